@@ -5,7 +5,7 @@ clips — one "step" = one full training step of the SAIS hot path on one batch 
     256 frames -> ViT-S/16 (12 blocks) -> 4-layer temporal encoder -> prototype (SupCon) loss
     -> backward through head, temporal encoder AND ViT -> (DP: RCCL all-reduce, overlapped) -> SGD step
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` with N > 1 and no torchrun environment: this process touches no GPU, starts
@@ -13,11 +13,18 @@ clips — one "step" = one full training step of the SAIS hot path on one batch 
 and exits with its code; fewer than N visible GPUs, or a torchrun WORLD_SIZE that differs from --gpus, is an
 error (non-zero exit), never a silent 1-rank run.
 
-Prints ONE JSON line on rank 0.  `value` = frames/s over all ranks with inputs resident in HBM;
-`roofline` = the MFMA kernel with the largest total time: algorithmic FLOP/s from HIP events on the launch
-stream (raw event intervals, measured in a separate instrumented pass after the timed region) against the
-dense bf16 MFMA peak; `cpu_baseline` = the CPU oracle (oracle/, the validated restatement of the reference)
-timed on this host's cores on a bounded sample (rank 0, N=1 only).
+Prints ONE JSON line on rank 0.  `value` = frames/s over all ranks with inputs resident in HBM, `ms_per_step` = the
+wall time of one of the K timed steps.  A plain run does only that: set-up, W warm-up steps, K timed steps, the line.
+
+`--dump-outputs DIR`: after the timed steps, what the last timed step computed goes to DIR/<name>.npy (float32 /
+float64, at most 64 MB; arrays larger than DUMP_SAMPLE elements as a fixed seeded sample of their entries).  Inputs and
+initial weights are seeded, so two builds run with the same arguments can be compared output for output.
+
+`--full` adds everything else, after the timed region: the hipGraph-vs-eager check, the in-run parity gate against the
+CPU oracle, `roofline` = the MFMA kernel with the largest total time: algorithmic FLOP/s from HIP events on the launch
+stream (raw event intervals, measured in a separate instrumented pass) against the dense bf16 MFMA peak, `comm` (N > 1),
+the sustained rate, `cpu_baseline` = the CPU oracle (oracle/, the validated restatement of the reference) timed on this
+host's cores on a bounded sample (rank 0, N=1 only), and the config 4 / 5 legs under `variants`.
 """
 import argparse
 import json
@@ -93,6 +100,12 @@ def parse_args():
     ap.add_argument("--sustain-seconds", type=float, default=10.0,
                     help="after the timed region, keep replaying the step for this long and report the settled rate "
                          "(clock under sustained MFMA load); 0 = skip")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, run every check and extra measurement: graph-vs-eager check, parity gate, "
+                         "per-kernel roofline pass, exchange timing, sustained rate, CPU baseline, variants (off: the "
+                         "line holds the timed figures only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0)")
     return ap.parse_args()
 
 
@@ -172,6 +185,35 @@ class CommEvents:
 
     def __init__(self):
         self.enabled, self.recs = False, []
+
+
+# ------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_SAMPLE = 1 << 20            # arrays with more elements are dumped as this many entries at fixed seeded positions
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_array(t, seed):
+    """A device or host tensor as a float32 numpy array of its own shape; with more than DUMP_SAMPLE elements, the 1-D array of
+    its entries at DUMP_SAMPLE fixed positions (numpy default_rng(seed), sorted) of the flattened tensor."""
+    import numpy as np
+    import torch
+    t = torch.as_tensor(t).detach()
+    if t.numel() > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(seed).choice(t.numel(), size=DUMP_SAMPLE, replace=False))
+        t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+    return t.float().cpu().numpy()
+
+
+def write_outputs(path, arrays):
+    """arrays: {name: numpy array} -> path/<name>.npy (float64 stays float64, everything else float32)."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})")
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 # ------------------------------------------------------------------------------------------ CPU baseline
@@ -275,6 +317,7 @@ def dino_main(args):
     """--workload dino: K steps of sais_amd.dino.train_step (teacher forward on the 2 global crops, student forward +
     backward on all crops, DINOLoss + centre, per-parameter clipping, AdamW, EMA teacher) on synthetic crops resident in
     HBM; one rank per GPU, gradients and the [1, out_dim] centre all-reduced over RCCL when N > 1 (weak scaling)."""
+    import numpy as np
     import torch
     import torch.distributed as dist
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -338,13 +381,23 @@ def dino_main(args):
         dist.all_reduce(dt, op=dist.ReduceOp.MAX)
     ms = dt.item() / args.steps * 1e3
     lv = loss.item()
+    if args.dump_outputs and rank == 0:        # the last timed step: its loss, the updated student / teacher, the centre
+        write_outputs(args.dump_outputs, {
+            "loss": np.array([float(loss)], dtype=np.float64),
+            "student_backbone_params": dump_array(student.backbone.flat.flat, 1),
+            "student_head_params": dump_array(student.head.flat.flat, 2),
+            "teacher_backbone_params": dump_array(teacher.backbone.flat.flat, 3),
+            "teacher_head_params": dump_array(teacher.head.flat.flat, 4),
+            "center": dump_array(loss_mod.center, 5)})
     comm_bytes = 4 * (student.backbone.flat.numel + student.head.flat.numel) if dist_on else 0
-    ops.TIMER = ops.KernelTimer()                                    # instrumented pass after the timed region (eager)
-    eager_step(args.warmup + args.steps)
-    torch.cuda.synchronize()
-    summ, ops.TIMER = ops.TIMER.summary(), None
-    top = max(summ.items(), key=lambda kv: kv[1]["total_ms"])
-    tf = top[1]["flops"] / (top[1]["avg_ms"] * 1e-3) / 1e12
+    summ = None
+    if args.full:
+        ops.TIMER = ops.KernelTimer()                                # instrumented pass after the timed region (eager)
+        eager_step(args.warmup + args.steps)
+        torch.cuda.synchronize()
+        summ, ops.TIMER = ops.TIMER.summary(), None
+        top = max(summ.items(), key=lambda kv: kv[1]["total_ms"])
+        tf = top[1]["flops"] / (top[1]["avg_ms"] * 1e-3) / 1e12
     if rank == 0:
         crops = f"2 x 224 + {nl} x 96"
         out = {"metric": "dino_pretrain_images_per_s", "value": round(B * world / (ms * 1e-3), 1), "unit": "images/s",
@@ -354,18 +407,19 @@ def dino_main(args):
                                       f"{crops} crops, out_dim {out_dim}, drop_path {args.vit_drop_path}, clip 3.0, AdamW, "
                                       f"EMA teacher", "parallelism": f"dp{world}", "launch": launch,
                           "student_token_rows_per_gpu": B * (2 * 197 + nl * 37), "teacher_token_rows_per_gpu": B * 2 * 197},
-               "loss": round(lv, 4), "peak_mem_gb": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2),
-               "roofline": {"kernel": top[0], "bound": "mfma", "achieved": round(tf, 1), "peak": MFMA_PEAK_TFLOPS,
-                            "unit": "TFLOP/s", "frac": round(tf / MFMA_PEAK_TFLOPS, 4), "traffic": None,
-                            "launches_per_step": top[1]["launches"], "avg_us": round(top[1]["avg_ms"] * 1e3, 1)},
-               "kernels_ms_per_step": {k: round(v["total_ms"], 3) for k, v in
-                                       sorted(summ.items(), key=lambda kv: -kv[1]["total_ms"])[:12]}}
+               "loss": round(lv, 4), "peak_mem_gb": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)}
+        if summ is not None:
+            out["roofline"] = {"kernel": top[0], "bound": "mfma", "achieved": round(tf, 1), "peak": MFMA_PEAK_TFLOPS,
+                               "unit": "TFLOP/s", "frac": round(tf / MFMA_PEAK_TFLOPS, 4), "traffic": None,
+                               "launches_per_step": top[1]["launches"], "avg_us": round(top[1]["avg_ms"] * 1e3, 1)}
+            out["kernels_ms_per_step"] = {k: round(v["total_ms"], 3) for k, v in
+                                          sorted(summ.items(), key=lambda kv: -kv[1]["total_ms"])[:12]}
         if dist_on:
             sync = getattr(opt, "_sync", None)
             out["comm"] = {"backend": "nccl (RCCL)", "world": world, "allreduce_bytes_per_step": comm_bytes,
                            "overlapped_with_backward": True, "centre_allreduce_bytes": 4 * out_dim,
                            "grad_sync": type(sync).__name__ if sync is not None else None}
-        if world == 1 and not dist_on and not args.no_cpu_baseline:
+        if args.full and world == 1 and not dist_on and not args.no_cpu_baseline:
             try:
                 avail = len(os.sched_getaffinity(0))
             except AttributeError:
@@ -483,6 +537,34 @@ def extract_main(args):
             dist.barrier()
             dist.destroy_process_group()
         return
+    if args.dump_outputs:                      # the last timed step: features, window embeddings and attention maps
+        write_outputs(args.dump_outputs, {
+            "rgb_features": dump_array(reps, 1), "flow_features": dump_array(freps, 2),
+            "window_embeddings": dump_array(torch.stack([torch.stack(list(r)) for r in out["reps"]]), 3),
+            "attention": dump_array(torch.cat(attention), 4)})
+    fps = world * N * args.steps / dt
+    nvit = N + max(1, N // 15)
+    out_line = {
+        "metric": "frames/sec ViT-S/16 long-video inference (extraction + sliding windows + attention export)",
+        "value": round(fps, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "bf16", "data": "synthetic",
+        "config": {"workload": f"BASELINE config 5: {N}-frame synthetic video per GPU, frozen ViT-S/16 forward in hipGraph-replayed "
+                               f"batches of {bs} (remainders and the {nvit - N} flow maps in "
+                               f"{'a batch of their own size' if tail == 'fit' else 'batches of %d' % (tail or bs)}), "
+                               f"{nwin} sliding windows x 3 TTA versions through the "
+                               f"two-stream 4-layer temporal encoder (window batch {args.window_batch}, main.sh's -bs), embeddings "
+                               f"+ attention maps [{nwin},16,16] exported to the host; random-init weights",
+                   "video_frames": N, "vit_frames_per_step": nvit, "windows": nwin, "parallelism": f"shards{world}",
+                   "launch": "hipGraph replay (ViT) + eager windows" if not args.no_graph else "eager"},
+        "frac_of_mfma_roofline": round(nvit * FLOP_PER_FRAME_FWD * args.steps / dt / 1e12 / MFMA_PEAK_TFLOPS, 4),
+    }
+    if not args.full:
+        print(json.dumps(out_line), flush=True)
+        if dist_on:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # where the step's time goes: the two halves timed separately (same inputs, after the timed region)
     torch.cuda.synchronize()
     t1 = time.perf_counter()
@@ -535,24 +617,9 @@ def extract_main(args):
     kern = max(summ, key=lambda t: summ[t]["total_ms"])
     k = summ[kern]
     ach = k["flops"] / (k["avg_ms"] * 1e-3) / 1e12
-    fps = world * N * args.steps / dt
-    nvit = N + max(1, N // 15)
-    out_line = {
-        "metric": "frames/sec ViT-S/16 long-video inference (extraction + sliding windows + attention export)",
-        "value": round(fps, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "bf16", "data": "synthetic",
-        "config": {"workload": f"BASELINE config 5: {N}-frame synthetic video per GPU, frozen ViT-S/16 forward in hipGraph-replayed "
-                               f"batches of {bs} (remainders and the {nvit - N} flow maps in "
-                               f"{'a batch of their own size' if tail == 'fit' else 'batches of %d' % (tail or bs)}), "
-                               f"{nwin} sliding windows x 3 TTA versions through the "
-                               f"two-stream 4-layer temporal encoder (window batch {args.window_batch}, main.sh's -bs), embeddings "
-                               f"+ attention maps [{nwin},16,16] exported to the host; random-init weights",
-                   "video_frames": N, "vit_frames_per_step": nvit, "windows": nwin, "parallelism": f"shards{world}",
-                   "launch": "hipGraph replay (ViT) + eager windows" if not args.no_graph else "eager"},
+    out_line.update({
         "split_ms": {"vit_extraction": round(ms_vit, 3), "windows_and_export": round(ms_win, 3)},
         "vit_forward_tflops": round(nvit * FLOP_PER_FRAME_FWD / (ms_vit * 1e-3) / 1e12, 1),
-        "frac_of_mfma_roofline": round(nvit * FLOP_PER_FRAME_FWD * args.steps / dt / 1e12 / MFMA_PEAK_TFLOPS, 4),
         "parity": parity,
         "roofline": {"bound": "mfma", "kernel": kern, "achieved": round(ach, 1), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
                      "frac": round(ach / MFMA_PEAK_TFLOPS, 4), "traffic": None, "algorithmic_bytes": int(k["bytes"]),
@@ -563,7 +630,7 @@ def extract_main(args):
                                              avg_us=round(v["avg_ms"] * 1e3, 1),
                                              tflops=round(v["flops"] / (v["avg_ms"] * 1e-3) / 1e12, 1),
                                              gbps=round(v["bytes"] / (v["avg_ms"] * 1e-3) / 1e9, 1)) for n, v in summ.items()}},
-    }
+    })
     if world == 1 and not args.no_cpu_baseline:
         try:
             avail = len(os.sched_getaffinity(0))
@@ -673,7 +740,8 @@ def run_variants(args):
     """BASELINE configs 4 and 5 beside the headline: two short child runs of this file (`--two-stream`, `--workload extract`; 5
     timed steps each, their own parity gates on), condensed.  Children, not in-process: each leg builds its own models and graphs
     and leaves nothing behind in this process; they start after the headline's timed and sustained regions."""
-    base = [sys.executable, os.path.abspath(__file__), "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-variants"]
+    base = [sys.executable, os.path.abspath(__file__), "--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline",
+            "--no-variants"]
     legs = {"config4_two_stream": base + ["--two-stream", "--sustain-seconds", "0"],
             "config5_long_video": base + ["--workload", "extract"]}
     out = {}
@@ -712,6 +780,7 @@ def main():
     if args.workload == "extract":
         return extract_main(args)
 
+    import numpy as np
     import torch
     import torch.distributed as dist
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -797,13 +866,22 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = tmax.item()
     timed_loss = float(loss.detach())
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed step gets from its last call: the loss and the model it updated (parameters after the SGD
+        # step, prototypes).  Not the raw gradients: after tens of SGD steps they differ by ~25 % between two runs of the same
+        # build (the fp32-atomic order of the dW sums, amplified by the trajectory), the parameters by ~1e-4
+        write_outputs(args.dump_outputs, {
+            "loss": np.array([timed_loss], dtype=np.float64),
+            "vit_params": dump_array(vit.flat.flat, 1), "temporal_params": dump_array(model.flat.flat, 2),
+            "prototypes": dump_array(torch.cat([p.detach().reshape(-1) for p in protos.values()]), 3)})
 
     # parity of the measured code path: one hipGraph replay and one eager step from the SAME weights and the same dropout
     # RNG state must give the same loss (the forward has no atomics, so this is exact up to nothing)
     graph_check = None
-    snap = [vit.flat.flat.clone(), model.flat.flat.clone()] + [p.detach().clone() for p in protos.values()]
-    rng_snap = None if model._rng is None else model._rng.clone()       # train-mode dropout: same masks for both runs
-    dp_snap = None if vit._rng is None else vit._rng.clone()            # ... and the same DropPath draws
+    if args.full:        # the state after the timed steps, put back before and after every check / extra measurement
+        snap = [vit.flat.flat.clone(), model.flat.flat.clone()] + [p.detach().clone() for p in protos.values()]
+        rng_snap = None if model._rng is None else model._rng.clone()       # train-mode dropout: same masks for both runs
+        dp_snap = None if vit._rng is None else vit._rng.clone()            # ... and the same DropPath draws
 
     def restore():
         with torch.no_grad():
@@ -817,7 +895,7 @@ def main():
                 p.copy_(s)
         vit.flat.refresh_shadows(vit._t_names)
         model.flat.refresh_shadows(model._t_names())
-    if use_graph and (rank == 0 or dist_on):      # N > 1: a step contains collectives, so every rank runs the check
+    if args.full and use_graph and (rank == 0 or dist_on):   # N > 1: a step contains collectives, so every rank runs it
         lg = float(step().detach())
         restore()
         le = float(eager_step().detach())
@@ -832,7 +910,7 @@ def main():
 
     # in-run parity gate (rank 0): the timed model on the timed inputs vs the CPU oracle, same draws
     parity = None
-    if rank == 0 and args.parity_clips > 0:
+    if args.full and rank == 0 and args.parity_clips > 0:
         restore()
         parity = parity_gate(vit, model, protos, frames, pad, labels, B, T, C, two, args.parity_clips)
         restore()
@@ -844,14 +922,15 @@ def main():
     # passes; only rank 0 brackets its kernels with events.
     roof = None
     NPASS = 3
-    if rank == 0:
-        ops.TIMER = ops.KernelTimer()
-    if comm_events is not None:
-        comm_events.enabled = True
-    if rank == 0 or dist_on:
-        for _ in range(NPASS):
-            eager_step()
-        torch.cuda.synchronize()
+    if args.full:
+        if rank == 0:
+            ops.TIMER = ops.KernelTimer()
+        if comm_events is not None:
+            comm_events.enabled = True
+        if rank == 0 or dist_on:
+            for _ in range(NPASS):
+                eager_step()
+            torch.cuda.synchronize()
     comm = None
     if comm_events is not None and comm_events.recs:
         r = comm_events.recs
@@ -874,7 +953,8 @@ def main():
             json.dump({"rank": rank, "world": world, "buckets": [list(b) for b in sync.last_buckets],
                        "frames_checksum": float(frames.double().sum()), "loss": timed_loss,
                        "payload": args.grad_payload}, fh)
-    if rank == 0:
+    pmc_all = pmc_stale = None
+    if args.full and rank == 0:
         summ = ops.TIMER.summary()
         ops.TIMER = None
         # the dominant kernel = the (kernel, shape) tag with the largest total time; a kernel that runs several shapes has
@@ -918,7 +998,7 @@ def main():
     # the snapshot before every chunk (untimed): a thousand SGD steps on random labels would otherwise drift to values
     # whose arithmetic no longer costs what real data costs.
     sustained = None
-    if args.sustain_seconds > 0:
+    if args.full and args.sustain_seconds > 0:
         n_chunk = max(args.steps, 10)
         ts0 = time.perf_counter()
         last_dt, total = 0.0, 0
@@ -987,13 +1067,16 @@ def main():
             "step_tflops": round(step_flops * world * args.steps / dt / 1e12, 1),
             "frac_of_mfma_roofline": round(step_flops * args.steps / dt / 1e12 / MFMA_PEAK_TFLOPS, 4),
             "loss": round(timed_loss, 6),
-            "sustained": None if sustained is None else dict(sustained, ratio_to_value=round(sustained["frames_per_s"] / fps, 4)),
-            "graph_vs_eager": graph_check,
-            "parity": parity,
-            "comm": comm,
-            "roofline": roof,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            out.update({
+                "sustained": None if sustained is None else dict(sustained, ratio_to_value=round(sustained["frames_per_s"] / fps, 4)),
+                "graph_vs_eager": graph_check,
+                "parity": parity,
+                "comm": comm,
+                "roofline": roof,
+            })
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 avail = len(os.sched_getaffinity(0))
             except AttributeError:
@@ -1005,7 +1088,7 @@ def main():
                         if not k.startswith(("clip_", "transEncoderClip", "attention", "finalModules", "linear2"))},
                        {k: v.detach().float().cpu() for k, v in protos.items()})
             out["cpu_baseline"] = cpu_baseline(T, C, max(1, min(avail, 32)), weights, Bfull=B)
-        if world == 1 and not dist_on and not two and not args.no_variants and os.environ.get("SAIS_BENCH_BACKEND", "nccl") == "nccl":
+        if args.full and world == 1 and not dist_on and not two and not args.no_variants and os.environ.get("SAIS_BENCH_BACKEND", "nccl") == "nccl":
             out["variants"] = run_variants(args)
         # a number from a numerically wrong step is not a result: the line says so and the exit code is non-zero
         bad = (parity is not None and not parity["pass"]) or bool(graph_check and graph_check.get("mismatch"))

@@ -140,18 +140,48 @@ def test_bench_gpus_flag_starts_n_ranks_or_fails_loudly():
     assert r.returncode != 0 and "WORLD_SIZE=2" in r.stderr
     if n >= 2:
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2",
-                            "--no-cpu-baseline", "--sustain-seconds", "0"], capture_output=True, text=True, cwd=ROOT)
+                            "--full", "--no-cpu-baseline", "--sustain-seconds", "0"], capture_output=True, text=True, cwd=ROOT)
         assert r.returncode == 0, r.stderr[-2000:]
         line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
         assert line["n_gpus"] == 2 and line["comm"]["allreduce_bytes_per_step"] > 100e6
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_outputs(tmp_path):
+    """A plain run (no --full) does set-up, warm-up and the timed steps and prints the timed figures only; --dump-outputs writes
+    what the last timed step computed (loss, updated parameters, prototypes) as float .npy files."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import numpy as np
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--clips", "1", "--frames", "8", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, cwd=ROOT, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["metric"]
+    assert d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert not {"roofline", "parity", "graph_vs_eager", "sustained", "comm", "cpu_baseline", "variants"} & set(d)
+    arrays = {f[:-len(".npy")]: np.load(out / f) for f in os.listdir(out)}
+    assert set(arrays) == {"loss", "vit_params", "temporal_params", "prototypes"}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert abs(float(arrays["loss"][0]) - d["loss"]) <= 1e-6 and arrays["vit_params"].shape == (1 << 20,)
+
+
+def _ranks_stderr(err, n=3000):
+    """The first traceback a rank printed (the launcher's summary at the end of stderr names the failed rank only) and the tail."""
+    i = err.find("Traceback")
+    return (err[i:i + n] + "\n[...]\n" if i >= 0 else "") + err[-n:]
 
 
 def _force_dist_bench(*extra):
     port = 29600 + (os.getpid() % 2000)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-                        "--gpus", "1", "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--sustain-seconds", "0",
-                        *extra],
+                        "--gpus", "1", "--steps", "3", "--warmup", "2", "--full", "--no-cpu-baseline", "--sustain-seconds",
+                        "0", *extra],
                        capture_output=True, text=True, cwd=ROOT, timeout=900,
                        env=dict(os.environ, SAIS_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert r.returncode == 0, r.stderr[-2000:]
@@ -194,10 +224,10 @@ def test_bench_two_ranks_complete_and_print_one_line(tmp_path):
     env = dict(os.environ, SAIS_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
                         "127.0.0.1", "--master-port", str(29700 + os.getpid() % 200), os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--steps", "2", "--warmup", "1", "--clips", "2", "--frames", "8",
+                        "--gpus", "2", "--steps", "2", "--warmup", "1", "--clips", "2", "--frames", "8", "--full",
                         "--sustain-seconds", "0"],
                        capture_output=True, text=True, cwd=ROOT, env=env, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
+    assert r.returncode == 0, _ranks_stderr(r.stderr, 2000)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
     d = json.loads(lines[0])
@@ -218,10 +248,10 @@ def test_bench_eight_ranks_over_gloo_on_one_gpu(tmp_path):
     env = dict(os.environ, SAIS_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", SAIS_BENCH_RANK_DUMP=str(dump))
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=8", "--master-addr",
                         "127.0.0.1", "--master-port", str(29900 + os.getpid() % 90), os.path.join(ROOT, "bench.py"),
-                        "--gpus", "8", "--steps", "2", "--warmup", "1", "--clips", "1", "--frames", "8",
+                        "--gpus", "8", "--steps", "2", "--warmup", "1", "--clips", "1", "--frames", "8", "--full",
                         "--sustain-seconds", "0", "--parity-clips", "0", "--grad-payload", "bf16"],
                        capture_output=True, text=True, cwd=ROOT, env=env, timeout=1500)
-    assert r.returncode == 0, r.stderr[-3000:]
+    assert r.returncode == 0, _ranks_stderr(r.stderr)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
     d = json.loads(lines[0])

@@ -485,6 +485,26 @@ def test_counter_files_go_stale_when_a_kernel_source_changes(tmp_path):
     assert bench.load_pmc("pmc_traffic.json", str(tmp_path))[1] is True
 
 
+def test_bench_dump_outputs_fixed_sample_within_limit(tmp_path):
+    """bench.py --dump-outputs: small arrays whole, large ones as the same seeded sample in every run, float32 / float64 on disk,
+    and a set of arrays over the 64 MB limit refused."""
+    import numpy as np
+    import bench
+    small = torch.arange(12, dtype=torch.bfloat16).view(3, 4)
+    assert np.array_equal(bench.dump_array(small, 0), small.float().numpy())
+    big = torch.randn(bench.DUMP_SAMPLE * 3, generator=torch.Generator().manual_seed(0))
+    a, b = bench.dump_array(big, 7), bench.dump_array(big.clone(), 7)
+    assert a.shape == (bench.DUMP_SAMPLE,) and a.dtype == np.float32 and np.array_equal(a, b)
+    assert not np.array_equal(a, bench.dump_array(big, 8))
+    assert np.isin(a, big.numpy()).all()
+    bench.write_outputs(str(tmp_path / "out"), {"loss": np.array([0.5]), "x": a, "i": np.arange(3)})
+    assert sorted(os.listdir(tmp_path / "out")) == ["i.npy", "loss.npy", "x.npy"]
+    assert np.load(tmp_path / "out" / "loss.npy").dtype == np.float64 and np.load(tmp_path / "out" / "i.npy").dtype == np.float32
+    with pytest.raises(SystemExit):
+        bench.write_outputs(str(tmp_path / "big"), {"x": np.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1, np.float32)})
+    assert not os.path.exists(tmp_path / "big")
+
+
 def test_feature_extractor_shapes_per_remainder():
     """FeatureExtractor.shape_for: the padded shape of a forward pass for `left` remaining frames under the three tail policies
     (no GPU: only the host arithmetic; the replay / eager bit-identity is tests/test_inference_gpu.py)."""

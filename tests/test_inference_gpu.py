@@ -356,7 +356,8 @@ def test_bench_extract_workload_prints_one_valid_line(gpu):
     parity gate against the CPU oracle green, the two halves timed, a roofline object for the dominant kernel."""
     import json
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "extract", "--steps", "2", "--warmup", "1",
-                        "--video-frames", "128", "--no-cpu-baseline"], capture_output=True, text=True, cwd=ROOT, timeout=900)
+                        "--video-frames", "128", "--full", "--no-cpu-baseline"], capture_output=True, text=True, cwd=ROOT,
+                       timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1

@@ -1,9 +1,9 @@
 #!/bin/bash
-# The driver's own command (python bench.py, default flags) with its wall time; prints the headline and the variants
+# The full benchmark run (python bench.py --full) with its wall time; prints the headline and the variants
 out=gpurun_out/${1:-bench_default}
 mkdir -p $out
 t0=$(date +%s)
-python bench.py > $out/bench.json 2> $out/bench.err
+python bench.py --full > $out/bench.json 2> $out/bench.err
 echo "rc=$? wall=$(( $(date +%s) - t0 )) s"
 python - <<PY
 import json

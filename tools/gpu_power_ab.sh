@@ -6,7 +6,7 @@ i=0
 for rep in 1 2; do
 for spec in "$@"; do
   i=$((i+1))
-  env $spec python bench.py --no-cpu-baseline --sustain-seconds 14 --steps 20 --warmup 3 --parity-clips 0 > $out/bench_$i.json 2> $out/bench_$i.err &
+  env $spec python bench.py --full --no-cpu-baseline --sustain-seconds 14 --steps 20 --warmup 3 --parity-clips 0 > $out/bench_$i.json 2> $out/bench_$i.err &
   BP=$!
   sleep 9
   for k in 1 2 3 4 5 6; do

@@ -2,7 +2,7 @@
 """profiles/pmc_mfma.json and profiles/pmc_traffic.json from rocprofv3 PMC passes over bench.py.
 
 On the GPU box (counters in their own passes, program directly after `--`, as MI355X_MICROARCH.md prescribes):
-    cd /tmp && export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; B="python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-graph"
+    cd /tmp && export TMPDIR=/tmp; R=<repository root>; B="python3 $R/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-graph"
     rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY \\
               SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $R/gpurun_out/pmc_sq -- $B
     rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $R/gpurun_out/pmc_fetch -- $B
@@ -143,7 +143,7 @@ def main():
             if g.get("SQ_LDS_IDX_ACTIVE") else None,
         }
     prov = provenance()
-    json.dump({"collected_with": "rocprofv3 --pmc (one SQ pass) -- python3 bench.py --steps 2 --warmup 1 --no-graph",
+    json.dump({"collected_with": "rocprofv3 --pmc (one SQ pass) -- python3 bench.py --steps 2 --warmup 1 --full --no-graph",
                "_provenance": prov, "kernels": mf}, open(os.path.join(ROOT, "profiles", "pmc_mfma.json"), "w"), indent=1)
     tr = {}
     for n in sorted(set(fetch) & set(write)):

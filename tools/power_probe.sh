@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/${1:-power}
 mkdir -p $O
 cd $R
-python bench.py --no-cpu-baseline --sustain-seconds 25 --steps 20 --warmup 3 > $O/bench.json 2> $O/bench.err &
+python bench.py --full --no-cpu-baseline --sustain-seconds 25 --steps 20 --warmup 3 > $O/bench.json 2> $O/bench.err &
 BP=$!
 sleep 12
 for i in $(seq 1 14); do

@@ -1,6 +1,6 @@
 """One training step of bench.py as the sequence of its kernel dispatches (rocprofv3 --kernel-trace CSV): which kernels sit next
 to the blit copies / fills, how many of each per step.  Usage (on the GPU box, after
-  rocprofv3 --kernel-trace --output-format csv -d <dir> -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --sustain-seconds 0 --parity-clips 0 --no-variants):
+  rocprofv3 --kernel-trace --output-format csv -d <dir> -- python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --sustain-seconds 0 --parity-clips 0 --no-variants):
   python tools/step_trace.py <dir> [pattern]"""
 import csv
 import glob
