@@ -26,36 +26,49 @@ class FrameError(Exception):
 
 
 def frame_batches(folder, dev, chunk=256, rank=0, world=1):
-    """SurgDataset.__getitem__ (dino-main/main_dino.py:295-316) + the transform of :158-162, with the arithmetic on the
-    GPU: JPEGs are decoded on the host (PIL), pushed as uint8 and turned into the float32 [n,3,224,224] ViT input by
-    sais_amd.preprocess (CenterCrop(0.8 H, 0.8 W) -> Resize((224,224)) -> ToTensor -> Normalize, bit-identical to the
-    torchvision 0.9.0 / Pillow pipeline of the reference).  Yields device tensors of up to `chunk` frames.
+    """SurgDataset.__getitem__ (dino-main/main_dino.py:295-316) + the transform of :158-162, on the GPU: the JPEG files'
+    bytes go to the device and are decoded there (sais_amd.jpeg, bit-identical to Pillow; files outside its supported set,
+    or with corrupt entropy data, are decoded by Pillow as before), then turned into the float32 [n,3,224,224] ViT input
+    by sais_amd.preprocess (CenterCrop(0.8 H, 0.8 W) -> Resize((224,224)) -> ToTensor -> Normalize, bit-identical to the
+    torchvision 0.9.0 / Pillow pipeline of the reference).  Yields device tensors of up to `chunk` frames of one geometry.
     world > 1: rank r decodes and embeds a contiguous range of the (sorted) frame files only."""
+    import io
     from sais_amd.parallel import shard_range
     from PIL import Image
+    from sais_amd.jpeg import JpegDecoder, parse_header
     from sais_amd.preprocess import FramePreprocessor
     plans, buf, geom = {}, [], None
+    dec = JpegDecoder(dev)
 
     def flush():
         h, w = geom
         if geom not in plans:
             plans[geom] = FramePreprocessor(h, w, 0.8, 0.8, MEAN, STD, device=dev)
-        return plans[geom](torch.from_numpy(np.stack(buf)))
+        blobs, headers = zip(*buf)
+        return plans[geom](dec.decode(list(blobs), list(headers)))
 
     files = sorted(glob.glob(os.path.join(folder, '*.jpg')))
     lo, hi = shard_range(len(files), rank, world)
     for p in files[lo:hi]:
-        with Image.open(p) as img:
-            if img.mode != 'RGB':                    # the reference drops the result of img.convert('RGB') (:297)
-                raise FrameError(f'{p}: mode {img.mode}; the pipeline expects RGB frames')
-            a = np.asarray(img)
-        if buf and (a.shape[:2] != geom or len(buf) == chunk):
+        with open(p, 'rb') as fh:
+            blob = fh.read()
+        hdr = parse_header(blob)
+        if hdr is not None:
+            g = (hdr.height, hdr.width)
+        else:
+            with Image.open(io.BytesIO(blob)) as img:
+                if img.mode != 'RGB':                # the reference drops the result of img.convert('RGB') (:297)
+                    raise FrameError(f'{p}: mode {img.mode}; the pipeline expects RGB frames')
+                g = (img.height, img.width)
+        if buf and (g != geom or len(buf) == chunk):
             yield flush()
             buf = []
-        geom = a.shape[:2]
-        buf.append(a)
+        geom = g
+        buf.append((blob, hdr))
     if buf:
         yield flush()
+    st = dec.stats
+    print(f'[extract] {folder}: {st["gpu"]} decoded on the GPU, {st["unsupported"] + st["failed"]} on the host', flush=True)
 
 
 def extract_flows(args, t0):

@@ -476,6 +476,54 @@ int  sais_preprocess_plan_box(const SaisPreprocessPlan* plan, int* box4 /* left,
 int  sais_preprocess_run(const SaisPreprocessPlan* plan, const unsigned char* frames, int nframes, float* out, void* stream);
 void sais_preprocess_plan_destroy(SaisPreprocessPlan* plan);
 
+/* ---------------------------------------------------------------- JPEG decode (compressed frames -> uint8 RGB)
+ * Image.open(path) + np.asarray of SurgDataset.__getitem__, dino-main/main_dino.py:295-316, as used by the feature
+ * extraction of extract_representations.py:158-162: baseline / extended-sequential Huffman JPEG, 8 bit, 3 components
+ * as YCbCr, luma 1x1 / 2x1 / 2x2 over chroma 1x1, one interleaved scan, any restart interval.  Output is bit-identical
+ * to libjpeg-turbo at Pillow's defaults (JDCT_ISLOW, fancy upsampling, jdcolor.c ycc_rgb_convert).  Anything else is
+ * SAIS_JPEG_UNSUPPORTED at parse time and stays with the caller's host decoder.
+ *
+ * sais_jpeg_parse is a host function (no GPU): it walks the markers with every length checked against n.
+ * sais_jpeg_decode only launches: the caller packs the files' bytes and one SaisJpegHeader per image (scan_offset
+ * rebased to the packed buffer) into device memory and passes a workspace of sais_jpeg_workspace_bytes.  status[i] is
+ * 0 for a decoded image, else a SAIS_JPEG_E* bit set: that image's output slot is undefined and the caller decodes
+ * the file on the host.  Corrupt entropy data never reads outside its own file's bytes.                          */
+#define SAIS_JPEG_UNSUPPORTED (-3)
+#define SAIS_JPEG_E_CODE 1           /* invalid Huffman code, or a coefficient size beyond 8-bit baseline   */
+#define SAIS_JPEG_E_RUN 2            /* AC run past k = 63                                                  */
+#define SAIS_JPEG_E_MARKER 4         /* RST out of sequence, unexpected marker, or no marker ends the scan  */
+#define SAIS_JPEG_E_SHORT 8          /* entropy data ends before the last MCU of a restart interval         */
+#define SAIS_JPEG_E_SYNC 16          /* speculative Huffman decode did not synchronise within the pass bound */
+#define SAIS_JPEG_E_RANGE 32         /* a dequantised coefficient outside int16 (not encoder output)         */
+typedef struct SaisJpegHuff {        /* one DHT table in decode form                                         */
+    uint16_t lookup[512];            /* next 9 bits -> (code length << 8) | symbol; 0 = a code longer than 9 */
+    int32_t maxcode[18];             /* largest code of length l (l = 1..16), -1 if none                     */
+    int32_t valoffset[18];           /* symbol of code c of length l = huffval[c + valoffset[l]]              */
+    uint8_t huffval[256];
+} SaisJpegHuff;
+typedef struct SaisJpegHeader {
+    int height, width;
+    int hsamp, vsamp;                /* luma sampling factors (chroma is 1x1)                                */
+    int restart_interval;            /* MCUs per restart interval, 0 = none                                  */
+    int mcu_count, segments;         /* MCUs of the image; restart segments = ceil(mcu_count / interval)     */
+    int qsel[3], dcsel[3], acsel[3]; /* table of each component                                              */
+    int64_t scan_offset;             /* first byte of the entropy-coded data                                 */
+    int64_t scan_bytes;              /* bytes from there to the end of the file (the scan ends at its marker) */
+    uint16_t quant[4][64];           /* natural order                                                        */
+    SaisJpegHuff dc[2], ac[2];
+} SaisJpegHeader;
+typedef struct SaisJpegBatch {
+    int n, height, width;            /* images of one geometry                                                */
+    int total_segments;              /* sum of the images' `segments`                                         */
+    int64_t total_scan_bytes;        /* sum of the images' scan_bytes                                         */
+    int64_t data_bytes;              /* size of the packed `data` buffer: every scan range must lie inside it */
+} SaisJpegBatch;
+int    sais_jpeg_parse(const unsigned char* data, size_t n, SaisJpegHeader* out);
+size_t sais_jpeg_workspace_bytes(int n, int height, int width, int64_t total_scan_bytes, int total_segments);
+int    sais_jpeg_decode(const SaisJpegBatch* batch, const unsigned char* data, const SaisJpegHeader* headers,
+                        void* workspace, size_t workspace_bytes, unsigned char* out /* [n,H,W,3] */, int* status,
+                        void* stream);
+
 /* ---------------------------------------------------------------- temporal encoder glue (dim 384, 4 heads x 96)
  * prepareInputForTransformer, prepare_model.py:179-195: z[b,0] = frame_cls, z[b,1+t] = x[b,t] + pos[t]
  * (out of place: the reference's in-place += on the caller's tensor is NOT reproduced).          */

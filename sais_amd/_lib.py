@@ -173,6 +173,9 @@ SIGNATURES = {
     "sais_preprocess_plan_box": [c_void_p, c_void_p],
     "sais_preprocess_run": [c_void_p, c_void_p, c_int, c_void_p, c_void_p],
     "sais_preprocess_plan_destroy": [c_void_p],
+    "sais_jpeg_parse": [c_void_p, ctypes.c_size_t, c_void_p],
+    "sais_jpeg_workspace_bytes": [c_int, c_int, c_int, ctypes.c_int64, c_int],
+    "sais_jpeg_decode": [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p],
     "sais_scale_f32": [c_void_p, c_long, c_float, c_void_p],
     "sais_touch": [c_void_p, c_long, c_void_p],
     "sais_temporal_prepare_fwd": [c_void_p, c_long, c_long, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
@@ -249,6 +252,7 @@ def load():
         fn.restype = c_int
     lib.sais_preprocess_plan_destroy.restype = None
     lib.sais_workspace_bytes.restype = ctypes.c_size_t
+    lib.sais_jpeg_workspace_bytes.restype = ctypes.c_size_t
     lib.sais_gemm_tn_grouped_slab_bytes.restype = ctypes.c_size_t
     lib.sais_last_error.restype = ctypes.c_char_p
     lib.sais_last_error.argtypes = []
