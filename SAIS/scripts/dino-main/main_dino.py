@@ -26,7 +26,7 @@ import torch.distributed as dist
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", ".."))
 from sais_amd import dino  # noqa: E402
-from sais_amd.dino_data import DataAugmentationDINO, SurgDataset  # noqa: E402
+from sais_amd.dino_data import DataAugmentationDINO, SurgDataset, collate_raw, gpu_crops  # noqa: E402
 
 
 def bool_flag(s):
@@ -66,6 +66,15 @@ def get_args_parser():
     return p
 
 
+def get_cli_parser():
+    """The command line: the reference's flags (get_args_parser) + switches of this implementation only."""
+    p = argparse.ArgumentParser("DINO", parents=[get_args_parser()])
+    p.add_argument("--gpu_augment", type=bool_flag, default=False,
+                   help="decode the frames and make the multi-crop views on the GPU (sais_amd.jpeg + sais_amd.augment): "
+                        "same views as the default Pillow loader for the same seed, bit for bit")
+    return p
+
+
 def init_distributed(args):
     """utils.init_distributed_mode (utils.py:468-500): torchrun / launch env, else a single process."""
     if "RANK" in os.environ and "WORLD_SIZE" in os.environ:
@@ -86,6 +95,26 @@ def collate(batch):
     return crops, [b[1] for b in batch], [b[2] for b in batch]
 
 
+def build_loader(args, dev):
+    """(dataset, sampler, loader, to_device): to_device turns the first element of a batch into the crop list on `dev`.
+    Default: DataLoader workers decode and augment with Pillow, the tensors are copied.  --gpu_augment: the workers read
+    the files and draw the views' parameters; decode and pixel work happen here, on the GPU, serially with the step."""
+    gpu_augment = getattr(args, "gpu_augment", False)
+    transform = DataAugmentationDINO(args.global_crops_scale, args.local_crops_scale, args.local_crops_number,
+                                     seed=args.seed * 1000 + args.rank)
+    dataset = SurgDataset(args.data_path, args.datasets, transform, frames_root=args.frames_root, gpu_augment=gpu_augment)
+    sampler = torch.utils.data.DistributedSampler(dataset, num_replicas=args.world_size, rank=args.rank, shuffle=True)
+    loader = torch.utils.data.DataLoader(dataset, sampler=sampler, batch_size=args.batch_size_per_gpu,
+                                         num_workers=args.num_workers, pin_memory=not gpu_augment, drop_last=True,
+                                         collate_fn=collate_raw if gpu_augment else collate)
+    if gpu_augment:
+        from sais_amd.augment import DinoAugmenter
+        from sais_amd.jpeg import JpegDecoder
+        decoder, augmenter = JpegDecoder(dev), DinoAugmenter(dev)
+        return dataset, sampler, loader, lambda items: gpu_crops(items, decoder, augmenter, dataset.crop_fracs())
+    return dataset, sampler, loader, lambda crops: [im.to(dev, non_blocking=True) for im in crops]
+
+
 def train_dino(args):
     init_distributed(args)
     torch.manual_seed(args.seed)
@@ -93,12 +122,7 @@ def train_dino(args):
     if args.arch.replace("deit", "vit") != "vit_small" or args.patch_size != 16 or args.optimizer != "adamw" or args.use_bn_in_head:
         raise NotImplementedError("MI355X path: --arch vit_small --patch_size 16 --optimizer adamw --use_bn_in_head false")
     dev = torch.device("cuda", args.gpu)
-    transform = DataAugmentationDINO(args.global_crops_scale, args.local_crops_scale, args.local_crops_number,
-                                     seed=args.seed * 1000 + args.rank)
-    dataset = SurgDataset(args.data_path, args.datasets, transform, frames_root=args.frames_root)
-    sampler = torch.utils.data.DistributedSampler(dataset, shuffle=True)
-    loader = torch.utils.data.DataLoader(dataset, sampler=sampler, batch_size=args.batch_size_per_gpu,
-                                         num_workers=args.num_workers, pin_memory=True, drop_last=True, collate_fn=collate)
+    dataset, sampler, loader, to_device = build_loader(args, dev)
     if main:
         print(f"Data loaded: there are {len(dataset)} images.")
     student, teacher = dino.build_student_teacher(args.out_dim, args.drop_path_rate, args.norm_last_layer, dev)
@@ -132,7 +156,7 @@ def train_dino(args):
         finite = torch.ones((), device=dev)                          # device-side AND of isfinite(loss), every iteration
         for i, (images, _, _) in enumerate(loader):
             it = niter * epoch + i
-            images = [im.to(dev, non_blocking=True) for im in images]
+            images = to_device(images)
             loss, _ = dino.train_step(student, teacher, dino_loss, optimizer, images, it, epoch, lr_schedule, wd_schedule,
                                       momentum_schedule, clip_grad=args.clip_grad, freeze_last_layer=args.freeze_last_layer)
             total += loss
@@ -167,7 +191,6 @@ def train_dino(args):
 
 
 if __name__ == "__main__":
-    parser = argparse.ArgumentParser("DINO", parents=[get_args_parser()])
-    args = parser.parse_args()
+    args = get_cli_parser().parse_args()
     os.makedirs(args.output_dir, exist_ok=True)
     train_dino(args)

@@ -524,6 +524,44 @@ int    sais_jpeg_decode(const SaisJpegBatch* batch, const unsigned char* data, c
                         void* workspace, size_t workspace_bytes, unsigned char* out /* [n,H,W,3] */, int* status,
                         void* stream);
 
+/* ---------------------------------------------------------------- DINO multi-crop augmentation (uint8 frames -> views)
+ * DataAugmentationDINO, dino-main/main_dino.py:633-679, on the frames SurgDataset.__getitem__ border-crops (:295-316):
+ * per view RandomResizedCrop (BICUBIC) -> flip -> ColorJitter -> grayscale -> GaussianBlur -> solarize -> ToTensor ->
+ * Normalize, bit-identical to the Pillow pipeline of sais_amd/dino_data.py for the same drawn parameters (one
+ * SaisAugView per view, drawn on the host by dino_data.draw_view).
+ *
+ * The view table is passed twice: `views_host` is checked by the entry (SAIS_ERR_ARG and no launch for a size above
+ * SAIS_AUG_MAX_SIZE, an empty box or one outside the border-cropped frame, a blur radius outside [0, 2], blend factors
+ * outside [0, 2], an order that is no permutation, offsets outside the buffers), `views_dev` is the same table in device
+ * memory, read by the kernels (which skip a view their copy shows to be out of range).  Both entries only launch.
+ *   sais_augment_crop_resize  frames uint8 [nframes,height,width,3]; border4 = left, top, width, height of the border
+ *                             crop; view i -> uint8 [size,size,3] at views_u8 + u8_offset
+ *   sais_augment_color        uint8 views -> float32 [3,size,size] at out + out_offset (elements); lut = device float
+ *                             [3][256], the normalised value of every byte per channel
+ *   sais_augment_workspace_bytes  size of the uint8 view buffer the table addresses (0 = bad table)                 */
+#define SAIS_AUG_MAX_SIZE 224
+typedef struct SaisAugView {
+    int frame;                       /* index into frames                                                     */
+    int box[4];                      /* left, top, right, bottom in the border-cropped frame                  */
+    int size;                        /* the view is size x size                                               */
+    int flip, jitter;
+    int order[4];                    /* jitter ops in application order: 0 brightness 1 contrast 2 saturation 3 hue */
+    float brightness, contrast, saturation;
+    int hue_shift;                   /* added to the H channel mod 256                                        */
+    int gray, blur;
+    float blur_radius;               /* GaussianBlur radius, used when blur != 0                              */
+    int solarize, reserved;
+    int64_t u8_offset;               /* bytes, into views_u8                                                  */
+    int64_t out_offset;              /* float elements, into out                                              */
+} SaisAugView;
+size_t sais_augment_workspace_bytes(const SaisAugView* views_host, int nviews);
+int    sais_augment_crop_resize(const unsigned char* frames, int nframes, int height, int width, const int* border4,
+                                const SaisAugView* views_host, const SaisAugView* views_dev, int nviews,
+                                unsigned char* views_u8, size_t views_u8_bytes, void* stream);
+int    sais_augment_color(const unsigned char* views_u8, size_t views_u8_bytes, const SaisAugView* views_host,
+                          const SaisAugView* views_dev, int nviews, const float* lut, float* out, size_t out_elems,
+                          void* stream);
+
 /* ---------------------------------------------------------------- temporal encoder glue (dim 384, 4 heads x 96)
  * prepareInputForTransformer, prepare_model.py:179-195: z[b,0] = frame_cls, z[b,1+t] = x[b,t] + pos[t]
  * (out of place: the reference's in-place += on the caller's tensor is NOT reproduced).          */

@@ -94,6 +94,13 @@ class SaisTemporalLayerBwd(ctypes.Structure):
          ("p_drop", c_float), ("rng_state", c_void_p), ("site0", ctypes.c_uint), ("dw_items_out", c_void_p)]
 
 
+class SaisAugView(ctypes.Structure):
+    _fields_ = [("frame", c_int), ("box", c_int * 4), ("size", c_int), ("flip", c_int), ("jitter", c_int),
+                ("order", c_int * 4), ("brightness", c_float), ("contrast", c_float), ("saturation", c_float),
+                ("hue_shift", c_int), ("gray", c_int), ("blur", c_int), ("blur_radius", c_float), ("solarize", c_int),
+                ("reserved", c_int), ("u8_offset", ctypes.c_int64), ("out_offset", ctypes.c_int64)]
+
+
 OP_VIT_BLOCK_FWD, OP_VIT_BLOCK_BWD, OP_TEMPORAL_LAYER_FWD, OP_TEMPORAL_LAYER_BWD = 0, 1, 2, 3
 
 
@@ -176,6 +183,11 @@ SIGNATURES = {
     "sais_jpeg_parse": [c_void_p, ctypes.c_size_t, c_void_p],
     "sais_jpeg_workspace_bytes": [c_int, c_int, c_int, ctypes.c_int64, c_int],
     "sais_jpeg_decode": [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p],
+    "sais_augment_workspace_bytes": [c_void_p, c_int],
+    "sais_augment_crop_resize": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                 ctypes.c_size_t, c_void_p],
+    "sais_augment_color": [c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_int, c_void_p, c_void_p, ctypes.c_size_t,
+                           c_void_p],
     "sais_scale_f32": [c_void_p, c_long, c_float, c_void_p],
     "sais_touch": [c_void_p, c_long, c_void_p],
     "sais_temporal_prepare_fwd": [c_void_p, c_long, c_long, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
@@ -253,6 +265,7 @@ def load():
     lib.sais_preprocess_plan_destroy.restype = None
     lib.sais_workspace_bytes.restype = ctypes.c_size_t
     lib.sais_jpeg_workspace_bytes.restype = ctypes.c_size_t
+    lib.sais_augment_workspace_bytes.restype = ctypes.c_size_t
     lib.sais_gemm_tn_grouped_slab_bytes.restype = ctypes.c_size_t
     lib.sais_last_error.restype = ctypes.c_char_p
     lib.sais_last_error.argtypes = []

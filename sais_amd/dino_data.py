@@ -11,6 +11,8 @@ ColorJitter's random order of brightness / contrast / saturation / hue, ...).  T
 import math
 import os
 import random
+from dataclasses import dataclass
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
@@ -26,50 +28,114 @@ def to_normalized_tensor(img):
     return torch.from_numpy((a - MEAN) / STD)
 
 
-def random_resized_crop(img, size, scale, rng, ratio=(3.0 / 4.0, 4.0 / 3.0)):
-    """transforms.RandomResizedCrop(size, scale=scale, interpolation=BICUBIC)."""
-    W, H = img.size
+BRIGHTNESS, CONTRAST, SATURATION, HUE = 0, 1, 2, 3                 # ColorJitter's ops, as numbered in ViewParams.order
+
+
+@dataclass(frozen=True)
+class ViewParams:
+    """Every random decision of one view; pixels are not involved (the draws depend on the frame's W x H only)."""
+    box: Tuple[int, int, int, int]           # left, top, right, bottom in the (border-cropped) image
+    size: int                                # the view is size x size
+    flip: bool
+    jitter: bool
+    order: Tuple[int, int, int, int]         # the jitter ops in the order they are applied
+    brightness: float
+    contrast: float
+    saturation: float
+    hue: float                               # the hue channel moves by int(hue * 255) mod 256
+    gray: bool
+    blur: Optional[float]                    # GaussianBlur radius
+    solarize: bool
+
+    @property
+    def hue_shift(self):
+        return int(self.hue * 255)
+
+
+def draw_crop_box(rng, W, H, scale, ratio=(3.0 / 4.0, 4.0 / 3.0)):
+    """The box of transforms.RandomResizedCrop: area / log-ratio sampling, 10 attempts, centre-crop fallback."""
     area = W * H
-    box = None
     for _ in range(10):
         target = area * rng.uniform(scale[0], scale[1])
         ar = math.exp(rng.uniform(math.log(ratio[0]), math.log(ratio[1])))
         w, h = int(round(math.sqrt(target * ar))), int(round(math.sqrt(target / ar)))
         if 0 < w <= W and 0 < h <= H:
             top, left = rng.randint(0, H - h), rng.randint(0, W - w)
-            box = (left, top, left + w, top + h)
-            break
-    if box is None:                                   # fallback: centre crop at the closest admissible ratio
-        r = W / H
-        if r < ratio[0]:
-            w, h = W, int(round(W / ratio[0]))
-        elif r > ratio[1]:
-            w, h = int(round(H * ratio[1])), H
-        else:
-            w, h = W, H
-        left, top = (W - w) // 2, (H - h) // 2
-        box = (left, top, left + w, top + h)
-    return img.crop(box).resize((size, size), Image.BICUBIC)
+            return (left, top, left + w, top + h)
+    r = W / H                                         # fallback: centre crop at the closest admissible ratio
+    if r < ratio[0]:
+        w, h = W, int(round(W / ratio[0]))
+    elif r > ratio[1]:
+        w, h = int(round(H * ratio[1])), H
+    else:
+        w, h = W, H
+    left, top = (W - w) // 2, (H - h) // 2
+    return (left, top, left + w, top + h)
 
 
-def color_jitter(img, rng, brightness=0.4, contrast=0.4, saturation=0.2, hue=0.1):
-    """transforms.ColorJitter: the four adjustments in a random order, factors uniform in [1 - x, 1 + x] ([-hue, hue])."""
-    ops = [0, 1, 2, 3]
+def random_resized_crop(img, size, scale, rng, ratio=(3.0 / 4.0, 4.0 / 3.0)):
+    """transforms.RandomResizedCrop(size, scale=scale, interpolation=BICUBIC)."""
+    W, H = img.size
+    return img.crop(draw_crop_box(rng, W, H, scale, ratio)).resize((size, size), Image.BICUBIC)
+
+
+def draw_color_jitter(rng, brightness=0.4, contrast=0.4, saturation=0.2, hue=0.1):
+    """The draws of transforms.ColorJitter: (order, brightness, contrast, saturation, hue)."""
+    ops = [BRIGHTNESS, CONTRAST, SATURATION, HUE]
     rng.shuffle(ops)
     fb, fc = rng.uniform(1 - brightness, 1 + brightness), rng.uniform(1 - contrast, 1 + contrast)
     fs, fh = rng.uniform(1 - saturation, 1 + saturation), rng.uniform(-hue, hue)
+    return tuple(ops), fb, fc, fs, fh
+
+
+def apply_color_jitter(img, ops, fb, fc, fs, fh):
     for op in ops:
-        if op == 0:
+        if op == BRIGHTNESS:
             img = ImageEnhance.Brightness(img).enhance(fb)
-        elif op == 1:
+        elif op == CONTRAST:
             img = ImageEnhance.Contrast(img).enhance(fc)
-        elif op == 2:
+        elif op == SATURATION:
             img = ImageEnhance.Color(img).enhance(fs)
         else:
             h, s, v = img.convert("HSV").split()
             hh = (np.asarray(h, dtype=np.int16) + int(fh * 255)) % 256
             img = Image.merge("HSV", (Image.fromarray(hh.astype(np.uint8), "L"), s, v)).convert("RGB")
     return img
+
+
+def color_jitter(img, rng, brightness=0.4, contrast=0.4, saturation=0.2, hue=0.1):
+    """transforms.ColorJitter: the four adjustments in a random order, factors uniform in [1 - x, 1 + x] ([-hue, hue])."""
+    return apply_color_jitter(img, *draw_color_jitter(rng, brightness, contrast, saturation, hue))
+
+
+def draw_view(rng, W, H, size, scale, blur_p, solarize_p=0.0):
+    """Every draw of one view of a W x H image, in the order DataAugmentationDINO has always consumed the generator:
+    crop attempts; flip; jitter gate, then shuffle + four factors only if it passed; grayscale gate; blur gate (<=), then
+    the radius only if it passed; the solarize gate only when solarize_p is non-zero."""
+    box = draw_crop_box(rng, W, H, scale)
+    flip = rng.random() < 0.5
+    jitter = rng.random() < 0.8
+    order, fb, fc, fs, fh = draw_color_jitter(rng) if jitter else ((BRIGHTNESS, CONTRAST, SATURATION, HUE), 1.0, 1.0, 1.0, 0.0)
+    gray = rng.random() < 0.2
+    blur = rng.uniform(0.1, 2.0) if rng.random() <= blur_p else None            # utils.GaussianBlur: radius ~ U(0.1, 2)
+    solarize = bool(solarize_p) and rng.random() < solarize_p                    # utils.Solarization
+    return ViewParams(box, size, flip, jitter, order, fb, fc, fs, fh, gray, blur, solarize)
+
+
+def apply_view_pillow(img, p):
+    """The pixel half of a view: what `p` decided, applied to the RGB image with Pillow -> normalised [3,size,size]."""
+    img = img.crop(p.box).resize((p.size, p.size), Image.BICUBIC)
+    if p.flip:
+        img = img.transpose(Image.FLIP_LEFT_RIGHT)
+    if p.jitter:
+        img = apply_color_jitter(img, p.order, p.brightness, p.contrast, p.saturation, p.hue)
+    if p.gray:
+        img = img.convert("L").convert("RGB")
+    if p.blur is not None:
+        img = img.filter(ImageFilter.GaussianBlur(radius=p.blur))
+    if p.solarize:
+        img = ImageOps.solarize(img)
+    return to_normalized_tensor(img)
 
 
 class DataAugmentationDINO:
@@ -99,41 +165,40 @@ class DataAugmentationDINO:
             self._rng_key = key
         return self._rng
 
-    def _flip_and_color_jitter(self, img):
-        r = self.rng
-        if r.random() < 0.5:
-            img = img.transpose(Image.FLIP_LEFT_RIGHT)
-        if r.random() < 0.8:
-            img = color_jitter(img, r)
-        if r.random() < 0.2:
-            img = img.convert("L").convert("RGB")
-        return img
+    def _view_specs(self):
+        return [(self.gsize, self.gscale, 1.0, 0.0), (self.gsize, self.gscale, 0.1, 0.2)] + \
+            [(self.lsize, self.lscale, 0.5, 0.0)] * self.local_crops_number
 
-    def _blur(self, img, p):
-        if self.rng.random() <= p:                                   # utils.GaussianBlur: radius ~ U(0.1, 2)
-            img = img.filter(ImageFilter.GaussianBlur(radius=self.rng.uniform(0.1, 2.0)))
-        return img
+    def draw(self, W, H):
+        """The ViewParams of the 2 global + local_crops_number local views of one W x H image; no pixel is touched."""
+        r = self.rng
+        return [draw_view(r, W, H, *spec) for spec in self._view_specs()]
 
     def _view(self, image, size, scale, blur_p, solarize_p=0.0):
-        img = random_resized_crop(image, size, scale, self.rng)
-        img = self._blur(self._flip_and_color_jitter(img), blur_p)
-        if solarize_p and self.rng.random() < solarize_p:            # utils.Solarization
-            img = ImageOps.solarize(img)
-        return to_normalized_tensor(img)
+        return apply_view_pillow(image, draw_view(self.rng, image.size[0], image.size[1], size, scale, blur_p, solarize_p))
 
     def __call__(self, image):
         image = image.convert("RGB")
-        crops = [self._view(image, self.gsize, self.gscale, 1.0), self._view(image, self.gsize, self.gscale, 0.1, 0.2)]
-        crops += [self._view(image, self.lsize, self.lscale, 0.5) for _ in range(self.local_crops_number)]
-        return crops
+        return [self._view(image, *spec) for spec in self._view_specs()]
+
+
+def border_box(W, H, fracs):
+    """transforms.CenterCrop((hf * H, wf * W)) of SurgDataset as (left, top, width, height)."""
+    hf, wf = fracs
+    ch, cw = int(hf * H), int(wf * W)
+    return int(round((W - cw) / 2.0)), int(round((H - ch) / 2.0)), cw, ch
 
 
 class SurgDataset(torch.utils.data.Dataset):
     """Frames listed in `<data_path>/paths/<dataset>_Paths.csv` (columns `path`, `label`; Windows separators allowed),
     border-cropped to the central 0.8 x 0.8 (0.8 x 0.7 for the *_Gronau sets) before the transform — main_dino.py:266-326
-    with its NS / VUA branch (every row is a training row; DINO needs no labels).  Returns (crops, label, dataset)."""
+    with its NS / VUA branch (every row is a training row; DINO needs no labels).  Returns (crops, label, dataset).
 
-    def __init__(self, data_path, dataset_list, transform, frames_root="./SAIS"):
+    With `gpu_augment` the workers only read the file and draw: an item is (file bytes, the header sais_jpeg_parse made
+    of them as bytes or None, the ViewParams of its views, label, dataset), and `gpu_crops` turns a batch of those into
+    the same crop list on the device."""
+
+    def __init__(self, data_path, dataset_list, transform, frames_root="./SAIS", gpu_augment=False):
         import pandas as pd
         rows = []
         for name in dataset_list:
@@ -142,6 +207,7 @@ class SurgDataset(torch.utils.data.Dataset):
                 rows.append((str(p).replace("\\", "/"), lab, name))
         self.rows, self.transform, self.frames_root = rows, transform, frames_root
         self.dataset = dataset_list[0]
+        self.gpu_augment = gpu_augment
 
     def crop_fracs(self):
         return (0.8, 0.7) if self.dataset in ("NS_Gronau", "VUA_Gronau") else (0.8, 0.8)
@@ -151,12 +217,71 @@ class SurgDataset(torch.utils.data.Dataset):
 
     def __getitem__(self, idx):
         path, label, name = self.rows[idx]
+        if self.gpu_augment:
+            return self._raw_item(os.path.join(self.frames_root, path), label, name)
         with open(os.path.join(self.frames_root, path), "rb") as f:
             img = Image.open(f)
             img.load()
         W, H = img.size
-        hf, wf = self.crop_fracs()
-        ch, cw = int(hf * H), int(wf * W)                            # transforms.CenterCrop((0.8 H, 0.8 W))
-        left, top = int(round((W - cw) / 2.0)), int(round((H - ch) / 2.0))
+        left, top, cw, ch = border_box(W, H, self.crop_fracs())      # transforms.CenterCrop((0.8 H, 0.8 W))
         img = img.crop((left, top, left + cw, top + ch))
         return self.transform(img), label, name
+
+    def _raw_item(self, path, label, name):
+        import io
+        from . import jpeg
+        with open(path, "rb") as f:
+            blob = f.read()
+        hdr = jpeg.parse_header(blob)
+        if hdr is not None:
+            W, H = hdr.width, hdr.height
+        else:
+            with Image.open(io.BytesIO(blob)) as img:                # reads the header only
+                W, H = img.size
+        _, _, cw, ch = border_box(W, H, self.crop_fracs())
+        return blob, None if hdr is None else bytes(hdr), self.transform.draw(cw, ch), label, name
+
+
+def collate_raw(batch):
+    """collate_fn of the gpu_augment mode: (items, labels, datasets); the items go to gpu_crops as they are."""
+    return batch, [b[3] for b in batch], [b[4] for b in batch]
+
+
+def gpu_crops(items, decoder, augmenter, fracs):
+    """A batch of gpu_augment items -> the crop list collate() makes of the Pillow path, on the device: one tensor
+    [B,3,s,s] per view.  JpegDecoder takes one geometry per call and a dataset list mixes sources, so the files are
+    grouped by geometry, decoded, augmented and scattered back into batch order.  A file the GPU decoder does not take
+    is decoded by Pillow, converted to RGB as DataAugmentationDINO.__call__ does, and uploaded."""
+    import io
+    from . import jpeg
+    dev = augmenter.device
+    headers, host, groups = [], {}, {}
+    for i, (blob, hdr, _, _, _) in enumerate(items):
+        h = None if hdr is None else jpeg.SaisJpegHeader.from_buffer_copy(hdr)
+        if h is None:
+            with Image.open(io.BytesIO(blob)) as img:
+                host[i] = np.array(img.convert("RGB"))
+        headers.append(h)
+        groups.setdefault((h.height, h.width) if h is not None else host[i].shape[:2], []).append(i)
+    crops = None
+    for (H, W), idx in groups.items():
+        on_gpu = [i for i in idx if headers[i] is not None]
+        if len(on_gpu) == len(idx):
+            frames = decoder.decode([items[i][0] for i in idx], [headers[i] for i in idx])
+        else:
+            frames = torch.empty(len(idx), H, W, 3, dtype=torch.uint8, device=dev)
+            if on_gpu:
+                dec = decoder.decode([items[i][0] for i in on_gpu], [headers[i] for i in on_gpu])
+                frames[torch.as_tensor([idx.index(i) for i in on_gpu], device=dev)] = dec
+            for k, i in enumerate(idx):
+                if i in host:
+                    frames[k].copy_(torch.from_numpy(host[i]))
+        views = augmenter(frames, [items[i][2] for i in idx], border_box(W, H, fracs))
+        if len(groups) == 1:
+            return views
+        if crops is None:
+            crops = [torch.empty(len(items), *v.shape[1:], dtype=v.dtype, device=dev) for v in views]
+        where = torch.as_tensor(idx, device=dev)
+        for c, v in zip(crops, views):
+            c[where] = v
+    return crops
