@@ -177,7 +177,6 @@ def mlp_fused_enabled(M):
     """SAIS_MLP_FUSED=1 runs the MLP branch of every ViT block as ONE launch per direction (sais_mlp_fwd / _bwd).  It is
     correct (same h / g' bits, same x_out up to fp32 summation order: tests/test_kernels_gpu.py) but MEASURED SLOWER than the
     launch pairs it replaces at the benchmark's size, so the default is the two-launch form."""
-    import os
     return os.environ.get("SAIS_MLP_FUSED", "0") == "1" and M >= MLP_FUSED_MIN_M
 
 
@@ -394,6 +393,18 @@ def vit_block_params(f, i, depth):
 def block_workspace(op, frames, ntok, device):
     n = L.load().sais_workspace_bytes(op, frames, ntok)
     return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def cached_workspace(cache, op, a, b, device, slot=0):
+    """block_workspace kept in the owner's `cache` dict per (op, shape, device, slot), outside hipGraph pools (while the stream
+    is capturing: a fresh buffer).  slot: the position of a backward call among those whose weight gradients are still to be
+    launched (their scratch must survive until that launch)."""
+    if torch.cuda.is_current_stream_capturing():
+        return block_workspace(op, a, b, device)
+    key = (op, a, b, str(device), slot)
+    if key not in cache:
+        cache[key] = block_workspace(op, a, b, device)
+    return cache[key]
 
 
 def vit_block_fwd(P, frames, ntok, xn1, x_in, qkv, attn_out, lse, x_mid, xn2, mean2, rstd2, h, gelu_grad, x_out, xn_next,

@@ -108,6 +108,7 @@ class fullModel(nn.Module):
         self._sig = None
         self._anchor = None
         self.grad_ready_hook = None
+        self._wsbuf = {}               # scratch of the layer-level calls (ops.cached_workspace)
         self._touched_T = 0            # longest stream whose position rows received a gradient since the last exchange
         # nn.TransformerEncoderLayer(d_model, nhead=4) keeps torch's default dropout = 0.1 (prepare_model.py:75); it acts
         # under model.train() (train.py:59) at four sites per layer.  Masks: Philox in the kernels (sais_hip.h), the
@@ -379,7 +380,7 @@ class fullModel(nn.Module):
                 m1, r1, m2, r2 = (e32(M), e32(M), e32(M), e32(M)) if save else (None, None, None, None)
                 ops.temporal_layer_fwd(self._layer_params(p), B, S, z, pad, qkv, ctx, attn if last else None, y1, z1, m1, r1, h,
                                        y2, zo, m2, r2, drop, (sidx * self.nlayers + l) * 4,
-                                       self._ws(L.OP_TEMPORAL_LAYER_FWD, B, S, dev))
+                                       ops.cached_workspace(self._wsbuf, L.OP_TEMPORAL_LAYER_FWD, B, S, dev))
                 if save:
                     layers.append(dict(z=z, qkv=qkv, ctx=ctx, y1=y1, m1=m1, r1=r1, z1=z1, h=h, y2=y2, m2=m2, r2=r2))
                 z = zo
@@ -418,18 +419,6 @@ class fullModel(nn.Module):
         if prefix not in self._lp:
             self._lp[prefix] = ops.temporal_layer_params(f, prefix)
         return self._lp[prefix]
-
-    def _ws(self, op, B, S, dev, slot=0):
-        """Scratch of a layer-level call; `slot` keeps the backward's per-layer workspaces apart (their weight-gradient
-        operands are read by ONE deferred launch after the last layer)."""
-        if torch.cuda.is_current_stream_capturing():
-            return ops.block_workspace(op, B, S, dev)
-        key = (op, B, S, str(dev), slot)
-        if not hasattr(self, "_wsbuf"):
-            self._wsbuf = {}
-        if key not in self._wsbuf:
-            self._wsbuf[key] = ops.block_workspace(op, B, S, dev)
-        return self._wsbuf[key]
 
     def _prefetch(self, backward):
         """The encoder's ~70 launches per step are a few microseconds each; their weights (35 MB fp32 forward, the same
@@ -510,7 +499,7 @@ class fullModel(nn.Module):
             if layer_calls:                              # one C call per layer (sais_temporal_layer_bwd)
                 ns = L.load().sais_tgemm_nsplit(M, D, 3 * D)
                 dx_slabs, dy1 = e32(ns, M, D), e32(M, D)
-                ws = self._ws(L.OP_TEMPORAL_LAYER_BWD, B, S, dev, slot=l)
+                ws = ops.cached_workspace(self._wsbuf, L.OP_TEMPORAL_LAYER_BWD, B, S, dev, slot=l)
                 ops.temporal_layer_bwd(self._layer_params(p), B, S, a, s["pad"], slabs, add, dx_slabs, dy1, drop, site, ws,
                                        dw_items=None if dw_items is None else (dw_items, 4 * l))
                 keep += [ws, dy1]

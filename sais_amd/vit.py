@@ -20,6 +20,7 @@ rates linspace(0, drop_path_rate, depth); SAIS itself only ever runs the ViT in 
 """
 import math
 import os
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -101,6 +102,44 @@ def _trunc_normal_(t, std=0.02):
     return nn.init.trunc_normal_(t, mean=0.0, std=std, a=-2.0, b=2.0)
 
 
+def _empty(dtype, dev):
+    return lambda *s: torch.empty(*s, dtype=dtype, device=dev)
+
+
+def _row_groups(imgs):
+    """One dict per resolution group: frames, tokens, its row / patch-row / frame offset in the stacked tensors and the same
+    ranges as slices (`rows`, `prows`, `frames`), the interpolation map (set by the embedding).  Returns also the three totals."""
+    groups, off, poff, foff = [], 0, 0, 0
+    for im in imgs:
+        Fr, ntok = im.shape[0], SIDES[im.shape[-1]]
+        n, npat = Fr * ntok, Fr * (ntok - 1)
+        groups.append(dict(Fr=Fr, ntok=ntok, off=off, poff=poff, foff=foff, interp=None, rows=slice(off, off + n),
+                           prows=slice(poff, poff + npat), frames=slice(foff, foff + Fr)))
+        off, poff, foff = off + n, poff + npat, foff + Fr
+    return groups, off, poff, foff
+
+
+class _PendingDW:
+    """Weight gradients of G blocks in ONE grouped launch (ops.dw_group, LABNOTES R6.8).  A deferred block leaves here what that
+    launch reads — the records of its C call (`calls`) or its four (p, q, dW, db) items (`items`) — and these keep its operands
+    alive until then (its du / d(mid) / dqkv, the bf16 gradient that entered it, the saved activations).  `extra`: the k / v
+    item of the CLS-only last block, which rides in the first launch (4 more tiles)."""
+
+    def __init__(self, model, saved, G, hooked):
+        self.model, self.saved = model, saved
+        self.takes_extra = G > 1 and not hooked
+        self.calls, self.items, self.extra, self.blocks = [], [], [], []
+
+    def flush(self):
+        if self.calls:
+            ops.vit_blocks_dw([c[:3] for c in self.calls], extra=self.extra)
+        elif self.items or self.extra:            # (extra alone: no block below the CLS-only one, depth 1)
+            ops.gemm_tn_grouped(self.items + self.extra, self.saved["M"])
+        for j in self.blocks:
+            self.model._block_finished(self.saved, j)
+        self.calls, self.items, self.extra, self.blocks = [], [], [], []
+
+
 class _ViTFn(torch.autograd.Function):
     """Whole-ViT forward/backward as one autograd node.  Parameter gradients are written by the HIP
     kernels into model.flat.grad (p.grad views) as a side effect; `anchor` only keeps the node alive."""
@@ -133,10 +172,9 @@ class VisionTransformer(nn.Module):
         # forward() returns norm(x)[:, 0] (:212-214): of the LAST block only the CLS rows are ever read, so its row-local half
         # (proj, norm2, MLP, residual adds) runs on the CLS rows and its attention for the CLS query only; outputs and all
         # parameter gradients are unchanged.  SAIS_VIT_PRUNE_LAST=0 / prune_last_block = False computes every row.
-        import os as _os
-        self.prune_last_block = _os.environ.get("SAIS_VIT_PRUNE_LAST", "1") != "0"
+        self.prune_last_block = os.environ.get("SAIS_VIT_PRUNE_LAST", "1") != "0"
         # one C call per Block (sais_vit_block_fwd / _bwd) instead of the per-launch Python sequence; SAIS_VIT_BLOCK_CALLS=0 off
-        self.block_calls = _os.environ.get("SAIS_VIT_BLOCK_CALLS", "1") != "0"
+        self.block_calls = os.environ.get("SAIS_VIT_BLOCK_CALLS", "1") != "0"
         self._bp, self._wsbuf = None, {}
         self._rng = None
         self.last_droppath_scales = None
@@ -243,174 +281,177 @@ class VisionTransformer(nn.Module):
         f = self.flat
         imgs = list(img) if isinstance(img, (list, tuple)) else [img]
         dev = imgs[0].device
-        e16 = lambda *s: torch.empty(*s, dtype=torch.bfloat16, device=dev)
-        e32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-        groups, off, poff, foff = [], 0, 0, 0          # per group: frames, tokens, row / patch-row / frame offsets, interp map
-        for im in imgs:
-            Fr, ntok = im.shape[0], SIDES[im.shape[-1]]
-            groups.append(dict(Fr=Fr, ntok=ntok, off=off, poff=poff, foff=foff, interp=None))
-            off, poff, foff = off + Fr * ntok, poff + Fr * (ntok - 1), foff + Fr
-        M, NP, Ftot = off, poff, foff
+        groups, M, NP, Ftot = _row_groups(imgs)
         if want_last_attn and len(groups) > 1:
             raise ValueError("get_last_selfattention takes one resolution")
-        patches = e16(NP, PATCH_K)
-        x = e32(M, D)
-        for im, g in zip(imgs, groups):
-            Fr, ntok = g["Fr"], g["ntok"]
-            pg = patches[g["poff"]:g["poff"] + Fr * (ntok - 1)]
-            xg = x[g["off"]:g["off"] + Fr * ntok].view(Fr, ntok, D)
-            ops.patchify(im, pg)
-            pos, g["interp"] = self._pos_table(im.shape[-1], dev)
-            ops.gemm_nt(pg, f.w("patch_embed.proj.weight").view(D, PATCH_K), L.EPI_PATCH_F32, xg,
-                        bias=f.w32("patch_embed.proj.bias"), aux=pos, grp=(ntok - 1, ntok, 1))
-            ops.vit_cls_rows(f.w32("cls_token"), pos, xg, Fr, ntok)
-        saved = {"patches": patches, "blocks": [], "groups": groups, "M": M, "Ftot": Ftot} if save else None
+        # Every decision of the pass, taken once; inside the loop only "is this the last block" is left.
+        pl = SimpleNamespace(groups=groups, M=M, NP=NP, Ftot=Ftot, dev=dev, save=save, e16=_empty(torch.bfloat16, dev),
+                             e32=_empty(torch.float32, dev))
         # Large M (training step, big extraction batches): the N = 384 GEMMs run on the row-owning kernel with the
         # FOLLOWING LayerNorm in their epilogue (sais_gemm_ln_fwd): proj -> norm2, fc2 -> the next block's norm1.
         # Only block 0's norm1 and the final norm remain stand-alone launches.
-        fused = M >= ops.ROW_GEMM_MIN_M
-        # DropPath (train mode): row scales keep_f / (1 - p_i) for the 2 x depth residual branches, one Philox draw per
-        # frame and branch; branch 2i = attention of block i, 2i + 1 = its MLP.  None in eval() / rate 0.
-        dp = None
-        if self.training and self.drop_path_rate > 0 and not want_last_attn:
-            if self._rng is None or self._rng.device != dev:
-                self._rng = ops.rng_state(self.drop_path_seed, dev)
-                rates = torch.linspace(0, self.drop_path_rate, self.depth).repeat_interleave(2)      # :150
-                self._dp_rates = rates.to(dev, torch.float32)
-            parts = []
-            for g in groups:                             # one advance + draw per group (what separate passes would do)
-                ops.rng_advance(self._rng)
-                parts.append(ops.droppath_scales(self._dp_rates, g["Fr"], g["ntok"], self._rng))
-            dp = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
-            self.last_droppath_scales = dp
-        if saved is not None:
-            saved["dp"] = dp
-        xn, qkv, ao, h = e16(M, D), e16(M, 3 * D), e16(M, D), e16(M, HID)
-        xn2 = e16(M, D)
-        mean1 = rstd1 = None
+        pl.fused = fused = M >= ops.ROW_GEMM_MIN_M
         # the CLS-only tail runs its [frames, 384] GEMMs on the split-K small-M kernel (SAIS_EPI_RAW_SLABS_F32: M < 8192 only), so a
         # pass with 8192 or more FRAMES computes the last block on every row like the others (pruned=False is
         # recorded in `saved`, the backward follows it)
-        prune = self.prune_last_block and not want_last_attn and Ftot < ops.ROW_GEMM_MIN_M
-        blockcall = self.block_calls and ops.TIMER is None and len(groups) == 1 and fused
+        pl.prune = self.prune_last_block and not want_last_attn and Ftot < ops.ROW_GEMM_MIN_M
+        pl.prune_q = pl.prune and len(groups) == 1 and _PRUNE_Q
+        pl.mlp_fused = ops.mlp_fused_enabled(M)
+        # One C call per Block (sais_vit_block_fwd: the launches of _block_fwd_launches, sequenced by the library) whenever
+        # nothing needs the per-launch view: no HIP-event instrumentation (bench.py's roofline pass), one resolution group
+        # (and not the block whose probabilities get_last_selfattention returns)
+        pl.block_call = self.block_calls and ops.TIMER is None and len(groups) == 1 and fused and not pl.mlp_fused
+        patches, x = self._embed_fwd(pl, imgs)
+        draw = self.training and self.drop_path_rate > 0 and not want_last_attn
+        dp = self._droppath_draw(groups, dev) if draw else None
+        saved = {"patches": patches, "blocks": [], "groups": groups, "M": M, "Ftot": Ftot, "dp": dp} if save else None
+        b = ln1 = None                                   # the block's tensors; (xn, mean1, rstd1) of its norm1
+        # norm1's outputs for a block: its own with `save`, else one xn for the whole pass and no statistics
+        norm1_out = lambda: (pl.e16(M, D), pl.e32(M), pl.e32(M)) if save else ln1 or (pl.e16(M, D), None, None)
         for i in range(self.depth):
             p = f"blocks.{i}."
-            last_attn = want_last_attn and i == self.depth - 1
-            if save:
-                if prune and i == self.depth - 1:
-                    qkv = e16(M, 3 * D)                  # the pruned last block keeps its compact tensors itself
-                else:
-                    qkv, ao, h = e16(M, 3 * D), e16(M, D), e16(M, HID)
+            last = i == self.depth - 1
             if i == 0 or not fused:                      # otherwise xn / mean1 / rstd1 came out of the previous fc2
-                if save:
-                    xn, mean1, rstd1 = e16(M, D), e32(M), e32(M)
-                ops.layernorm_fwd(x, M, D, f.w32(p + "norm1.weight"), f.w32(p + "norm1.bias"), 1e-6, y16=xn, mean=mean1,
-                                  rstd=rstd1)
-            use_block = blockcall and not last_attn and not ops.mlp_fused_enabled(M) and not (prune and i == self.depth - 1)
-            if prune and i == self.depth - 1 and len(groups) == 1 and _PRUNE_Q:
-                # CLS-only last block: keys and values of every token, the query of the CLS rows only (the other rows' q
-                # columns of `qkv` stay unwritten: nothing reads them)
+                ln1 = norm1_out()
+                ops.layernorm_fwd(x, M, D, f.w32(p + "norm1.weight"), f.w32(p + "norm1.bias"), 1e-6, y16=ln1[0], mean=ln1[1],
+                                  rstd=ln1[2])
+            if pl.prune and last:                        # the CLS-only last block: its qkv here, the rest in _cls_tail_fwd
+                xn = ln1[0]
+                qkv = pl.e16(M, 3 * D) if save or b is None else b["qkv"]      # (with `save` it keeps its tensors itself)
                 Wq, bq = f.w(p + "attn.qkv.weight"), f.w32(p + "attn.qkv.bias")
-                ops.gemm_nt(xn, Wq[D:], L.EPI_BIAS_BF16, qkv[:, D:], bias=bq[D:])
-                g0 = groups[0]
-                ops.gemm_nt(xn.view(g0["Fr"], g0["ntok"], D)[:, 0], Wq[:D], L.EPI_BIAS_BF16,
-                            qkv.view(g0["Fr"], g0["ntok"], 3 * D)[:, 0, :D], bias=bq[:D])
-            elif not use_block:
-                ops.gemm_nt(xn, f.w(p + "attn.qkv.weight"), L.EPI_BIAS_BF16, qkv, bias=f.w32(p + "attn.qkv.bias"))
-            if prune and i == self.depth - 1:
-                reps, tail = self._cls_tail_fwd(f, i, x, xn, mean1, rstd1, qkv, groups, dp, save, e16, e32)
+                if pl.prune_q:
+                    # keys and values of every token, the query of the CLS rows only (the other rows' q columns of `qkv` stay
+                    # unwritten: nothing reads them)
+                    ops.gemm_nt(xn, Wq[D:], L.EPI_BIAS_BF16, qkv[:, D:], bias=bq[D:])
+                    g0 = groups[0]
+                    ops.gemm_nt(xn.view(g0["Fr"], g0["ntok"], D)[:, 0], Wq[:D], L.EPI_BIAS_BF16,
+                                qkv.view(g0["Fr"], g0["ntok"], 3 * D)[:, 0, :D], bias=bq[:D])
+                else:
+                    ops.gemm_nt(xn, Wq, L.EPI_BIAS_BF16, qkv, bias=bq)
+                reps, tail = self._cls_tail_fwd(f, i, x, *ln1, qkv, groups, dp, save, pl.e16, pl.e32)
                 if save:
                     saved["blocks"].append(tail)
                     saved.update(x_final=tail["x_out"], meanN=tail["meanN"], rstdN=tail["rstdN"], pruned=True)
                 return reps, saved
-            # One C call per Block (sais_vit_block_fwd: the launches below, sequenced by the library) whenever nothing needs the
-            # per-launch view: no HIP-event instrumentation (bench.py's roofline pass), one resolution group, no probabilities
-            if use_block:
+            if save or b is None:                        # without `save` one set of tensors serves every block
+                b = self._block_buffers(pl, x, ln1)
+            if want_last_attn and last:
+                return self._attn_fwd(pl, i, b, want_probs=True), None
+            nxt = norm1_out() if fused and not last else None
+            x_out = pl.e32(M, D) if save else x          # (without `save` the residual stream is updated in place)
+            rs_attn, rs_mlp = (None, None) if dp is None else (dp[2 * i], dp[2 * i + 1])
+            if pl.block_call:
                 g0 = groups[0]
-                lse0 = e32(g0["Fr"], HEADS, g0["ntok"]) if save else None
-                x_mid = e32(M, D) if save else x
-                x_out = e32(M, D) if save else x
-                if save:
-                    xn2 = e16(M, D)
-                mean2, rstd2 = (e32(M), e32(M)) if save else (None, None)
-                u = ops.gelu_grad_buffer(M, HID, x.device) if save else None
-                nxt = i + 1 < self.depth
-                blk = dict(x_in=x, mean1=mean1, rstd1=rstd1, xn1=xn, qkv=qkv, ao=ao, lse=[lse0], x_mid=x_mid, mean2=mean2,
-                           rstd2=rstd2, xn2=xn2, dgelu=u, h=h) if save else None
-                xn_in = xn
-                if nxt and save:
-                    xn, mean1, rstd1 = e16(M, D), e32(M), e32(M)
-                ops.vit_block_fwd(self._block_params(i), g0["Fr"], g0["ntok"], xn_in, x, qkv, ao, lse0, x_mid, xn2, mean2, rstd2,
-                                  h if save else None, u, x_out, xn if nxt else None, mean1 if nxt else None,
-                                  rstd1 if nxt else None, None if dp is None else dp[2 * i],
-                                  None if dp is None else dp[2 * i + 1], None if save else self._ws(L.OP_VIT_BLOCK_FWD, g0, dev))
-                if save:
-                    saved["blocks"].append(blk)
-                x = x_out
-                continue
-            lse, probs = [], None
-            for g in groups:
-                Fr, ntok, lo = g["Fr"], g["ntok"], g["off"]
-                lg = e32(Fr, HEADS, ntok) if save else None
-                probs = e32(Fr, HEADS, ntok, ntok) if last_attn else None
-                ops.vit_attn_fwd(qkv[lo:lo + Fr * ntok], Fr, ao[lo:lo + Fr * ntok], lg, probs, ntok=ntok)
-                lse.append(lg)
-            if last_attn:
-                return probs, None
-            x_mid = e32(M, D) if save else x
-            if save:
-                xn2 = e16(M, D)
-            mean2 = e32(M) if save else None
-            rstd2 = e32(M) if save else None
-            rs_attn = None if dp is None else dp[2 * i]
-            rs_mlp = None if dp is None else dp[2 * i + 1]
-            if fused:
-                ops.gemm_ln_fwd(ao, f.w(p + "attn.proj.weight"), f.w32(p + "attn.proj.bias"), x, x_mid, xn2,
-                                f.w32(p + "norm2.weight"), f.w32(p + "norm2.bias"), 1e-6, mean2, rstd2, rowscale=rs_attn)
+                ws = None if save else ops.cached_workspace(self._wsbuf, L.OP_VIT_BLOCK_FWD, g0["Fr"], g0["ntok"], dev)
+                ops.vit_block_fwd(self._block_params(i), g0["Fr"], g0["ntok"], b["xn1"], x, b["qkv"], b["ao"], b["lse"][0],
+                                  b["x_mid"], b["xn2"], b["mean2"], b["rstd2"], b["h"], b["dgelu"], x_out,
+                                  *(nxt or (None, None, None)), rs_attn, rs_mlp, ws)
             else:
-                ops.gemm_nt(ao, f.w(p + "attn.proj.weight"), L.EPI_BIAS_RESID_F32, x_mid,
-                            bias=f.w32(p + "attn.proj.bias"), aux=x, rowscale=rs_attn)
-                ops.layernorm_fwd(x_mid, M, D, f.w32(p + "norm2.weight"), f.w32(p + "norm2.bias"), 1e-6, y16=xn2,
-                                  mean=mean2, rstd=rstd2)
-            u = ops.gelu_grad_buffer(M, HID, x.device) if save else None
-            x_out = e32(M, D) if save else x
-            blk = dict(x_in=x, mean1=mean1, rstd1=rstd1, xn1=xn, qkv=qkv, ao=ao, lse=lse, x_mid=x_mid, mean2=mean2,
-                       rstd2=rstd2, xn2=xn2, dgelu=u, h=h) if save else None
-            nxt = fused and i + 1 < self.depth
-            if nxt and save:
-                xn, mean1, rstd1 = e16(M, D), e32(M), e32(M)
-            q = f"blocks.{i + 1}." if nxt else None
-            if ops.mlp_fused_enabled(M):
-                # the whole MLP branch in ONE launch: fc1 + GELU (+ GELU') -> fc2 + residual (+ the next block's norm1); h is
-                # written for the backward pass but never read back, and in inference it is not materialised at all
-                ops.mlp_fwd(xn2, f.w(p + "mlp.fc1.weight"), f.w32(p + "mlp.fc1.bias"), f.w(p + "mlp.fc2.weight"),
-                            f.w32(p + "mlp.fc2.bias"), x_mid, x_out, h=h if save else None, g=u,
-                            xn_out=xn if nxt else None, gamma=f.w32(q + "norm1.weight") if nxt else None,
-                            beta=f.w32(q + "norm1.bias") if nxt else None, eps=1e-6, mean=mean1 if nxt else None,
-                            rstd=rstd1 if nxt else None, rowscale=rs_mlp)
-            else:
-                ops.gemm_nt(xn2, f.w(p + "mlp.fc1.weight"), ops.epi_gelu_grad(M) if save else L.EPI_BIAS_GELU_BF16, h,
-                            bias=f.w32(p + "mlp.fc1.bias"), out2=u)
-                if nxt:
-                    ops.gemm_ln_fwd(h, f.w(p + "mlp.fc2.weight"), f.w32(p + "mlp.fc2.bias"), x_mid, x_out, xn,
-                                    f.w32(q + "norm1.weight"), f.w32(q + "norm1.bias"), 1e-6, mean1, rstd1, rowscale=rs_mlp)
-                else:
-                    ops.gemm_nt(h, f.w(p + "mlp.fc2.weight"), L.EPI_BIAS_RESID_F32, x_out, bias=f.w32(p + "mlp.fc2.bias"),
-                                aux=x_mid, rowscale=rs_mlp)
+                self._block_fwd_launches(pl, i, b, x_out, nxt, rs_attn, rs_mlp)
             if save:
-                saved["blocks"].append(blk)
-            x = x_out
-        reps = e32(Ftot, D)
-        meanN = e32(Ftot) if save else None
-        rstdN = e32(Ftot) if save else None
-        for g in groups:                                 # final norm on the CLS rows only (row stride = ntok * 384)
-            Fr, ntok, lo, fo = g["Fr"], g["ntok"], g["off"], g["foff"]
-            ops.layernorm_fwd(x[lo:lo + Fr * ntok], Fr, ntok * D, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6,
-                              y32=reps[fo:fo + Fr], mean=None if meanN is None else meanN[fo:fo + Fr],
-                              rstd=None if rstdN is None else rstdN[fo:fo + Fr])
+                saved["blocks"].append(b)
+            x, ln1 = x_out, nxt or ln1
+        reps, meanN, rstdN = self._final_norm_fwd(pl, x)
         if save:
             saved.update(x_final=x, meanN=meanN, rstdN=rstdN)
         return reps, saved
+
+    def _embed_fwd(self, pl, imgs):
+        """Patchify, patch GEMM (+ bias + positional table) and CLS rows per group -> (patches bf16 [NP, 768], x f32 [M, 384])."""
+        f = self.flat
+        patches = pl.e16(pl.NP, PATCH_K)
+        x = pl.e32(pl.M, D)
+        for im, g in zip(imgs, pl.groups):
+            Fr, ntok = g["Fr"], g["ntok"]
+            pg = patches[g["prows"]]
+            xg = x[g["rows"]].view(Fr, ntok, D)
+            ops.patchify(im, pg)
+            pos, g["interp"] = self._pos_table(im.shape[-1], pl.dev)
+            ops.gemm_nt(pg, f.w("patch_embed.proj.weight").view(D, PATCH_K), L.EPI_PATCH_F32, xg,
+                        bias=f.w32("patch_embed.proj.bias"), aux=pos, grp=(ntok - 1, ntok, 1))
+            ops.vit_cls_rows(f.w32("cls_token"), pos, xg, Fr, ntok)
+        return patches, x
+
+    def _droppath_draw(self, groups, dev):
+        """DropPath (train mode): row scales keep_f / (1 - p_i) for the 2 x depth residual branches, one Philox draw per
+        frame and branch; branch 2i = attention of block i, 2i + 1 = its MLP.  f32 [2 x depth, M]."""
+        if self._rng is None or self._rng.device != dev:
+            self._rng = ops.rng_state(self.drop_path_seed, dev)
+            rates = torch.linspace(0, self.drop_path_rate, self.depth).repeat_interleave(2)      # :150
+            self._dp_rates = rates.to(dev, torch.float32)
+        parts = []
+        for g in groups:                                 # one advance + draw per group (what separate passes would do)
+            ops.rng_advance(self._rng)
+            parts.append(ops.droppath_scales(self._dp_rates, g["Fr"], g["ntok"], self._rng))
+        dp = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+        self.last_droppath_scales = dp
+        return dp
+
+    @staticmethod
+    def _block_buffers(pl, x, ln1):
+        """The tensors of one block, for the C call or the launch list; with `save` this dict is what the backward gets.  Without,
+        the stream is updated in place and only the launch list needs h (the C call keeps GELU(u) in its workspace)."""
+        M, save, e16, e32 = pl.M, pl.save, pl.e16, pl.e32
+        return dict(x_in=x, mean1=ln1[1], rstd1=ln1[2], xn1=ln1[0], qkv=e16(M, 3 * D), ao=e16(M, D),
+                    lse=[e32(g["Fr"], HEADS, g["ntok"]) if save else None for g in pl.groups],
+                    x_mid=e32(M, D) if save else x, mean2=e32(M) if save else None, rstd2=e32(M) if save else None,
+                    xn2=e16(M, D), dgelu=ops.gelu_grad_buffer(M, HID, pl.dev) if save else None,
+                    h=e16(M, HID) if save or not pl.block_call else None)
+
+    def _attn_fwd(self, pl, i, b, want_probs=False):
+        """qkv and the attention of block i, per group.  want_probs: get_last_selfattention's exit — the attention also writes
+        its probabilities f32 [frames, heads, ntok, ntok], which are returned (one group)."""
+        f, p, probs = self.flat, f"blocks.{i}.", None
+        ops.gemm_nt(b["xn1"], f.w(p + "attn.qkv.weight"), L.EPI_BIAS_BF16, b["qkv"], bias=f.w32(p + "attn.qkv.bias"))
+        for g, lg in zip(pl.groups, b["lse"]):
+            if want_probs:
+                probs = pl.e32(g["Fr"], HEADS, g["ntok"], g["ntok"])
+            ops.vit_attn_fwd(b["qkv"][g["rows"]], g["Fr"], b["ao"][g["rows"]], lg, probs, ntok=g["ntok"])
+        return probs
+
+    def _block_fwd_launches(self, pl, i, b, x_out, nxt, rs_attn, rs_mlp):
+        """One block as its launches; nxt: where fc2's epilogue puts the next block's norm1, or None."""
+        f, p, M, save = self.flat, f"blocks.{i}.", pl.M, pl.save
+        x, x_mid, xn2, h, u = b["x_in"], b["x_mid"], b["xn2"], b["h"], b["dgelu"]
+        self._attn_fwd(pl, i, b)
+        if pl.fused:
+            ops.gemm_ln_fwd(b["ao"], f.w(p + "attn.proj.weight"), f.w32(p + "attn.proj.bias"), x, x_mid, xn2,
+                            f.w32(p + "norm2.weight"), f.w32(p + "norm2.bias"), 1e-6, b["mean2"], b["rstd2"], rowscale=rs_attn)
+        else:
+            ops.gemm_nt(b["ao"], f.w(p + "attn.proj.weight"), L.EPI_BIAS_RESID_F32, x_mid,
+                        bias=f.w32(p + "attn.proj.bias"), aux=x, rowscale=rs_attn)
+            ops.layernorm_fwd(x_mid, M, D, f.w32(p + "norm2.weight"), f.w32(p + "norm2.bias"), 1e-6, y16=xn2,
+                              mean=b["mean2"], rstd=b["rstd2"])
+        xn, mean1, rstd1 = nxt or (None, None, None)
+        q = f"blocks.{i + 1}." if nxt else None
+        if pl.mlp_fused:
+            # the whole MLP branch in ONE launch: fc1 + GELU (+ GELU') -> fc2 + residual (+ the next block's norm1); h is
+            # written for the backward pass but never read back, and in inference it is not materialised at all
+            ops.mlp_fwd(xn2, f.w(p + "mlp.fc1.weight"), f.w32(p + "mlp.fc1.bias"), f.w(p + "mlp.fc2.weight"),
+                        f.w32(p + "mlp.fc2.bias"), x_mid, x_out, h=h if save else None, g=u, xn_out=xn,
+                        gamma=f.w32(q + "norm1.weight") if nxt else None, beta=f.w32(q + "norm1.bias") if nxt else None,
+                        eps=1e-6, mean=mean1, rstd=rstd1, rowscale=rs_mlp)
+        else:
+            ops.gemm_nt(xn2, f.w(p + "mlp.fc1.weight"), ops.epi_gelu_grad(M) if save else L.EPI_BIAS_GELU_BF16, h,
+                        bias=f.w32(p + "mlp.fc1.bias"), out2=u)
+            if nxt:
+                ops.gemm_ln_fwd(h, f.w(p + "mlp.fc2.weight"), f.w32(p + "mlp.fc2.bias"), x_mid, x_out, xn,
+                                f.w32(q + "norm1.weight"), f.w32(q + "norm1.bias"), 1e-6, mean1, rstd1, rowscale=rs_mlp)
+            else:
+                ops.gemm_nt(h, f.w(p + "mlp.fc2.weight"), L.EPI_BIAS_RESID_F32, x_out, bias=f.w32(p + "mlp.fc2.bias"),
+                            aux=x_mid, rowscale=rs_mlp)
+
+    def _final_norm_fwd(self, pl, x):
+        """The final norm on the CLS rows only (row stride = ntok * 384).  Returns (reps f32 [frames, 384], mean, rstd)."""
+        f, Ftot = self.flat, pl.Ftot
+        reps = pl.e32(Ftot, D)
+        meanN, rstdN = (pl.e32(Ftot), pl.e32(Ftot)) if pl.save else (None, None)
+        for g in pl.groups:
+            fr = g["frames"]
+            ops.layernorm_fwd(x[g["rows"]], g["Fr"], g["ntok"] * D, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6,
+                              y32=reps[fr], mean=None if meanN is None else meanN[fr],
+                              rstd=None if rstdN is None else rstdN[fr])
+        return reps, meanN, rstdN
 
     def _block_params(self, i):
         """ctypes parameter blocks of the Blocks (pointers into the flat buffers), rebuilt when those are."""
@@ -420,16 +461,6 @@ class VisionTransformer(nn.Module):
             self._bp = (key, [ops.vit_block_params(f, j, self.depth) for j in range(self.depth)])
         return self._bp[1][i]
 
-    def _ws(self, op, grp, dev, slot=0):
-        """Scratch for a block-level call (sais_workspace_bytes), kept per (op, shape, slot) outside hipGraph pools.  slot: the
-        position of a backward call among those whose weight gradients are still to be launched (their scratch must survive)."""
-        if torch.cuda.is_current_stream_capturing():
-            return ops.block_workspace(op, grp["Fr"], grp["ntok"], dev)
-        key = (op, grp["Fr"], grp["ntok"], str(dev), slot)
-        if key not in self._wsbuf:
-            self._wsbuf[key] = ops.block_workspace(op, grp["Fr"], grp["ntok"], dev)
-        return self._wsbuf[key]
-
     def _cls_tail_fwd(self, f, i, x, xn1, mean1, rstd1, qkv, groups, dp, save, e16, e32):
         """The last block from its qkv on, restricted to what forward() returns (the CLS rows): attention for the CLS query
         (sais_vit_attn_cls_fwd, one launch per resolution group), then proj + residual, norm2, fc1 + GELU, fc2 + residual and
@@ -438,9 +469,8 @@ class VisionTransformer(nn.Module):
         Ftot = sum(g["Fr"] for g in groups)
         ao = e16(Ftot, D)
         for g in groups:
-            Fr, ntok, lo, fo = g["Fr"], g["ntok"], g["off"], g["foff"]
-            ops.vit_attn_cls_fwd(qkv[lo:lo + Fr * ntok], Fr, ao[fo:fo + Fr], ntok)
-        cls_rows = lambda t, w: [t[g["off"]:g["off"] + g["Fr"] * g["ntok"]].view(g["Fr"], g["ntok"], *w)[:, 0] for g in groups]
+            ops.vit_attn_cls_fwd(qkv[g["rows"]], g["Fr"], ao[g["frames"]], g["ntok"])
+        cls_rows = lambda t, w: [t[g["rows"]].view(g["Fr"], g["ntok"], *w)[:, 0] for g in groups]
         one = len(groups) == 1
         x_cls = cls_rows(x, (D,))[0] if one else torch.cat(cls_rows(x, (D,)))
         rs_attn = None if dp is None else torch.cat(cls_rows(dp[2 * i], ())).contiguous()
@@ -464,7 +494,7 @@ class VisionTransformer(nn.Module):
                     xn2=xn2, dgelu=u, h=h, rs_attn=rs_attn, rs_mlp=rs_mlp, x_out=x_out, meanN=meanN, rstdN=rstdN) if save else None
         return reps, tail
 
-    def _cls_tail_bwd(self, f, saved, dreps, dx, dxa, dqkv, fused, defer=None):
+    def _cls_tail_bwd(self, f, saved, dreps, dx, dxa, dqkv, fused, pend):
         """Backward of _cls_tail_fwd: the gradient enters on the CLS rows only.  Everything row-local stays on [frames, 384]
         tensors; the attention backward (sais_vit_attn_cls_bwd) writes the whole dqkv (dk, dv of every token, dq of the CLS
         rows, zeros elsewhere); the dX of qkv + norm1's backward then writes EVERY row of dx / dxa, taking the residual-stream
@@ -476,7 +506,7 @@ class VisionTransformer(nn.Module):
         groups, M = saved["groups"], saved["M"]
         Ftot = sum(g["Fr"] for g in groups)
         dev = dreps.device
-        e16 = lambda *sh: torch.empty(*sh, dtype=torch.bfloat16, device=dev)
+        e16 = _empty(torch.bfloat16, dev)
         dx_c = torch.empty(Ftot, D, dtype=torch.float32, device=dev)
         ops.layernorm_bwd(s["x_out"], D, s["meanN"], s["rstdN"], f.w32("norm.weight"), Ftot, dy32=dreps, dx32=dx_c,
                           dgamma=f.g("norm.weight"), dbeta=f.g("norm.bias"))
@@ -493,8 +523,7 @@ class VisionTransformer(nn.Module):
                           dx16=dxb_c, dgamma=f.g(p + "norm2.weight"), dbeta=f.g(p + "norm2.bias"), rowscale16=s["rs_attn"])
         ops.gemm_nt_splitk(dxb_c, f.wt16[p + "attn.proj.weight"], 6, out16=dao)
         for g in groups:
-            Fr, ntok, lo, fo = g["Fr"], g["ntok"], g["off"], g["foff"]
-            ops.vit_attn_cls_bwd(s["qkv"][lo:lo + Fr * ntok], dao[fo:fo + Fr], Fr, dqkv[lo:lo + Fr * ntok], ntok)
+            ops.vit_attn_cls_bwd(s["qkv"][g["rows"]], dao[g["frames"]], g["Fr"], dqkv[g["rows"]], g["ntok"])
         compact = [
             (dxa_c, s["h"], f.g(p + "mlp.fc2.weight"), f.g(p + "mlp.fc2.bias")),
             (du, s["xn2"], f.g(p + "mlp.fc1.weight"), f.g(p + "mlp.fc1.bias")),
@@ -505,8 +534,8 @@ class VisionTransformer(nn.Module):
             compact.append((dqkv.view(Fr, ntok, 3 * D)[:, 0, :D], s["xn1"].view(Fr, ntok, D)[:, 0], gW[:D], gb[:D]))
             ops.gemm_tn_grouped(compact, Ftot)
             kv = (dqkv[:, D:], s["xn1"], gW[D:], gb[D:])
-            if defer is not None:                     # rides in the first grouped launch of the blocks below (4 more tiles)
-                defer.append(kv)
+            if pend.takes_extra:                      # rides in the first grouped launch of the blocks below (4 more tiles)
+                pend.extra.append(kv)
             else:
                 ops.gemm_tn_grouped([kv], M)
         else:
@@ -516,175 +545,161 @@ class VisionTransformer(nn.Module):
         rs_prev = None if dp is None or i == 0 else dp[2 * (i - 1) + 1]
         if fused and all(g["Fr"] * g["ntok"] >= ops.ROW_GEMM_MIN_M for g in groups):
             for g in groups:
-                Fr, ntok, lo, fo = g["Fr"], g["ntok"], g["off"], g["foff"]
-                hi = lo + Fr * ntok
-                ops.gemm_ln_bwd(dqkv[lo:hi], f.wt16[p + "attn.qkv.weight"], s["x_in"][lo:hi], s["mean1"][lo:hi], s["rstd1"][lo:hi],
-                                f.w32(p + "norm1.weight"), dres=dx_c[fo:fo + Fr], dres_period=ntok, dx32=dx[lo:hi],
-                                dx16=dxa[lo:hi], dgamma=f.g(p + "norm1.weight"), dbeta=f.g(p + "norm1.bias"),
-                                rowscale16=None if rs_prev is None else rs_prev[lo:hi],
-                                xn16=s["xn1"][lo:hi], beta=f.w32(p + "norm1.bias"))
+                r = g["rows"]
+                ops.gemm_ln_bwd(dqkv[r], f.wt16[p + "attn.qkv.weight"], s["x_in"][r], s["mean1"][r], s["rstd1"][r],
+                                f.w32(p + "norm1.weight"), dres=dx_c[g["frames"]], dres_period=g["ntok"], dx32=dx[r],
+                                dx16=dxa[r], dgamma=f.g(p + "norm1.weight"), dbeta=f.g(p + "norm1.bias"),
+                                rowscale16=None if rs_prev is None else rs_prev[r],
+                                xn16=s["xn1"][r], beta=f.w32(p + "norm1.bias"))
         else:                                         # small M: scatter the CLS gradient into a zeroed residual-stream gradient
             dx.zero_()
             for g in groups:
-                Fr, ntok, lo, fo = g["Fr"], g["ntok"], g["off"], g["foff"]
-                dx[lo:lo + Fr * ntok].view(Fr, ntok, D)[:, 0].copy_(dx_c[fo:fo + Fr])
+                dx[g["rows"]].view(g["Fr"], g["ntok"], D)[:, 0].copy_(dx_c[g["frames"]])
             dxn_full = e16(M, D)
             ops.gemm_nt(dqkv, f.wt16[p + "attn.qkv.weight"], L.EPI_BIAS_BF16, dxn_full)
             ops.layernorm_bwd(s["x_in"], D, s["mean1"], s["rstd1"], f.w32(p + "norm1.weight"), M, dy16=dxn_full, dres=dx,
                               dx32=dx, dx16=dxa, dgamma=f.g(p + "norm1.weight"), dbeta=f.g(p + "norm1.bias"),
                               rowscale16=rs_prev)
-        saved["blocks"][i] = None
-        if self.grad_ready_hook:                      # (with a hook nothing of this block is deferred: _backward_kernels)
-            self.grad_ready_hook(*self.block_grad_range(i))
+        # (the k / v weight gradient above may still be pending in `pend`, which happens only without an ACTIVE hook: a hook that
+        # carries active = False is then told about this block before that gradient is written — ADVICE r6 #3)
+        self._block_finished(saved, i)
 
     # ------------------------------------------------------------------ backward kernels
+    def _block_finished(self, saved, i):
+        """Block i's backward is issued: drop what the forward saved; its gradient slice is final, DP all-reduce may start."""
+        saved["blocks"][i] = None
+        if self.grad_ready_hook:
+            self.grad_ready_hook(*self.block_grad_range(i))
+
     def _backward_kernels(self, saved, dreps):
         f = self.flat
         f.attach_grads()
         dev = dreps.device
-        groups, M = saved["groups"], saved["M"]
-        e16 = lambda *s: torch.empty(*s, dtype=torch.bfloat16, device=dev)
+        groups, M, dp = saved["groups"], saved["M"], saved.get("dp")
+        e16 = _empty(torch.bfloat16, dev)
+        # Every decision of the pass, taken once (from this pass's own inputs, not from what the forward decided).
         pruned = bool(saved.get("pruned"))
         fused = M >= ops.ROW_GEMM_MIN_M
-        dxa, dxb = e16(M, D), e16(M, D)            # bf16 copies of the residual-stream gradient (block input / mid)
-        # Weight gradients of G blocks in ONE grouped launch (LABNOTES R6.8): a block's dW needs ten M-splits to fill the chip with
-        # its 24 tiles, each split writing a partial tile that a second launch sums; 24 G tiles need 10 / G.  The operands of a
-        # deferred block (its du / d(mid) / dqkv, the bf16 gradient that entered it, the saved activations) stay alive until then.
-        G = 1
+        mlp_fused = ops.mlp_fused_enabled(M)
+        block_call = self.block_calls and ops.TIMER is None and len(groups) == 1 and fused and not mlp_fused
         # a data-parallel hook that all-reduces the blocks' gradients while the backward goes on (an idle one — GradSync in a world
         # of one — carries active = False)
         hooked = self.grad_ready_hook is not None and getattr(self.grad_ready_hook, "active", True)
-        if fused and M % 32 == 0 and not ops.mlp_fused_enabled(M):      # (several resolution groups: the per-launch path below)
-            G = ops.dw_group(dp_hooks=hooked)
-        pend_extra = []
+        # blocks per weight-gradient launch (_PendingDW); 1: every block launches its own
+        G = ops.dw_group(dp_hooks=hooked) if fused and M % 32 == 0 and not mlp_fused else 1
+        pl = SimpleNamespace(groups=groups, M=M, e16=e16, fused=fused, mlp_fused=mlp_fused, defer=G > 1)
+        pend = _PendingDW(self, saved, G, hooked)
+        dxa = e16(M, D)                            # bf16 copy of the residual-stream gradient that enters a block
+        # scratch of the launch list (the C call has its workspace; dqkv also serves the CLS-only block): dxb = the bf16 gradient at
+        # a block's middle.  With deferred weight gradients du / dqkv / dxb are operands of the pending launch: a set per block
+        shared = not (block_call or pl.defer)
+        t = SimpleNamespace(dqkv=e16(M, 3 * D) if pruned or shared else None, du=e16(M, HID) if shared else None,
+                            dxb=e16(M, D) if shared else None, dxn=None if block_call or fused else e16(M, D),
+                            dao=None if block_call else e16(M, D))
         if pruned:                                  # every row of dx is WRITTEN by the last block's dX qkv + norm1' kernel
             dx = torch.empty(M, D, dtype=torch.float32, device=dev)
-            dqkv0 = e16(M, 3 * D)
-            self._cls_tail_bwd(f, saved, dreps, dx, dxa, dqkv0, fused,
-                               defer=pend_extra if G > 1 and not hooked else None)
+            self._cls_tail_bwd(f, saved, dreps, dx, dxa, t.dqkv, fused, pend)
         else:
             dx = torch.zeros(M, D, dtype=torch.float32, device=dev)
-        for g in ([] if pruned else groups):
-            Fr, ntok, lo, fo = g["Fr"], g["ntok"], g["off"], g["foff"]
-            ops.layernorm_bwd(saved["x_final"][lo:lo + Fr * ntok], ntok * D, saved["meanN"][fo:fo + Fr],
-                              saved["rstdN"][fo:fo + Fr], f.w32("norm.weight"), Fr, dy32=dreps[fo:fo + Fr],
-                              dx32=dx[lo:lo + Fr * ntok], lddx32=ntok * D, dgamma=f.g("norm.weight"),
-                              dbeta=f.g("norm.bias"))
-        dp = saved.get("dp")
-        # with DropPath the gradient that enters a branch is s dx (the residual stream keeps dx): the bf16 copies carry the
-        # NEXT branch's scale — dxa feeds an MLP branch (2i + 1), dxb an attention branch (2i)
-        if pruned:
-            pass
-        elif dp is None:
-            ops.cast_bf16(dx, dxa)
-        else:
-            ops.cast_bf16_rows(dx, dp[2 * (self.depth - 1) + 1], dxa)
-        dxn, dao, du = (None if fused else e16(M, D)), e16(M, D), e16(M, HID)
-        dqkv = dqkv0 if pruned else e16(M, 3 * D)
-        if self.grad_ready_hook and not pruned:
-            self.grad_ready_hook(f.offsets["norm.weight"], f.numel)
-        pend_calls, pend_items, pend_blocks = [], [], []
-
-        def flush_dw():
-            if pend_calls:
-                ops.vit_blocks_dw([c[:3] for c in pend_calls], extra=pend_extra)
-                pend_extra.clear()
-            if pend_items:
-                ops.gemm_tn_grouped(pend_items + pend_extra, M)
-                pend_extra.clear()
-            for j in pend_blocks:
-                saved["blocks"][j] = None
-                if self.grad_ready_hook:              # the block's gradient slice is final: DP all-reduce may start
-                    self.grad_ready_hook(*self.block_grad_range(j))
-            pend_calls.clear(); pend_items.clear(); pend_blocks.clear()
-
+            self._final_norm_bwd(saved, dreps, dx, dxa)
         for i in reversed(range(self.depth - 1 if pruned else self.depth)):
-            p = f"blocks.{i}."
             s = saved["blocks"][i]
             rs_attn = None if dp is None else dp[2 * i]                        # this block's attention branch
             rs_prev = None if dp is None or i == 0 else dp[2 * (i - 1) + 1]     # the MLP branch of block i - 1
-            if self.block_calls and ops.TIMER is None and len(groups) == 1 and fused and not ops.mlp_fused_enabled(M):
-                g0 = groups[0]
-                if G > 1:
-                    dxa_out = e16(M, D)
-                    ws = self._ws(L.OP_VIT_BLOCK_BWD, g0, dev, slot=len(pend_calls))
-                    a = ops.vit_block_bwd(self._block_params(i), g0["Fr"], g0["ntok"], s, dx, dxa, dxa_out, rs_attn, rs_prev,
-                                          s["lse"][0], ws, defer_dw=True)
-                    pend_calls.append((self._block_params(i), a, ws, dxa, s))          # dxa, s: kept alive for the launch
-                    pend_blocks.append(i)
-                    dxa = dxa_out
-                    if len(pend_blocks) == G or i == 0:
-                        flush_dw()
-                    continue
-                ops.vit_block_bwd(self._block_params(i), g0["Fr"], g0["ntok"], s, dx, dxa, dxa, rs_attn, rs_prev, s["lse"][0],
-                                  self._ws(L.OP_VIT_BLOCK_BWD, g0, dev))
-                saved["blocks"][i] = None
-                if self.grad_ready_hook:
-                    self.grad_ready_hook(*self.block_grad_range(i))
-                continue
-            if G > 1:                                 # per-launch path with deferred dW: this block's gradient tensors are its own
-                du, dqkv, dxb = e16(M, HID), e16(M, 3 * D), e16(M, D)
-            # MLP branch
-            if fused and ops.mlp_fused_enabled(M):    # dX of fc2 x GELU' -> dX of fc1 -> norm2's backward: ONE launch
-                ops.mlp_bwd(dxa, f.wt16[p + "mlp.fc2.weight"], s["dgelu"], f.wt16[p + "mlp.fc1.weight"], du, s["x_mid"],
-                            s["mean2"], s["rstd2"], f.w32(p + "norm2.weight"), dres=dx, dx32=dx, dx16=dxb,
-                            dgamma=f.g(p + "norm2.weight"), dbeta=f.g(p + "norm2.bias"), rowscale16=rs_attn)
-            elif fused:       # dX of fc1 with norm2's backward (+ residual gradient) in its epilogue
-                ops.gemm_nt(dxa, f.wt16[p + "mlp.fc2.weight"], ops.epi_mul(M), du, aux=s["dgelu"])
-                ops.gemm_ln_bwd(du, f.wt16[p + "mlp.fc1.weight"], s["x_mid"], s["mean2"], s["rstd2"],
-                                f.w32(p + "norm2.weight"), dres=dx, dx32=dx, dx16=dxb, dgamma=f.g(p + "norm2.weight"),
-                                dbeta=f.g(p + "norm2.bias"), rowscale16=rs_attn, xn16=s["xn2"], beta=f.w32(p + "norm2.bias"))
+            # deferred: dxa stays an operand of the pending launch, the NEXT block's bf16 gradient is written beside it
+            dxa_out = e16(M, D) if pl.defer else dxa
+            if block_call:
+                g0, P = groups[0], self._block_params(i)
+                ws = ops.cached_workspace(self._wsbuf, L.OP_VIT_BLOCK_BWD, g0["Fr"], g0["ntok"], dev, slot=len(pend.calls))
+                a = ops.vit_block_bwd(P, g0["Fr"], g0["ntok"], s, dx, dxa, dxa_out, rs_attn, rs_prev, s["lse"][0], ws,
+                                      defer_dw=pl.defer)
+                if pl.defer:
+                    pend.calls.append((P, a, ws, dxa, s))                      # dxa, s: kept alive for the launch
             else:
-                ops.gemm_nt(dxa, f.wt16[p + "mlp.fc2.weight"], ops.epi_mul(M), du, aux=s["dgelu"])
-                ops.gemm_nt(du, f.wt16[p + "mlp.fc1.weight"], L.EPI_BIAS_BF16, dxn)
-                ops.layernorm_bwd(s["x_mid"], D, s["mean2"], s["rstd2"], f.w32(p + "norm2.weight"), M, dy16=dxn, dres=dx,
-                                  dx32=dx, dx16=dxb, dgamma=f.g(p + "norm2.weight"), dbeta=f.g(p + "norm2.bias"),
-                                  rowscale16=rs_attn)
-            # attention branch
-            ops.gemm_nt(dxb, f.wt16[p + "attn.proj.weight"], L.EPI_BIAS_BF16, dao)
-            for g, lg in zip(groups, s["lse"]):
-                Fr, ntok, lo = g["Fr"], g["ntok"], g["off"]
-                hi = lo + Fr * ntok
-                ops.vit_attn_bwd(s["qkv"][lo:hi], dao[lo:hi], s["ao"][lo:hi], lg, None, Fr, dqkv[lo:hi], ntok=ntok)
-            # all four weight / bias gradients of the block in one launch.  (A side stream for this launch was measured
-            # in round 1: 20.4 vs 19.6 ms/step — both kernels fill the chip — and removed.)
-            dw = [(dxa, s["h"], f.g(p + "mlp.fc2.weight"), f.g(p + "mlp.fc2.bias")),
-                  (du, s["xn2"], f.g(p + "mlp.fc1.weight"), f.g(p + "mlp.fc1.bias")),
-                  (dxb, s["ao"], f.g(p + "attn.proj.weight"), f.g(p + "attn.proj.bias")),
-                  (dqkv, s["xn1"], f.g(p + "attn.qkv.weight"), f.g(p + "attn.qkv.bias"))]
-            if G > 1:
-                pend_items += dw
-                pend_blocks.append(i)
-                dxa = e16(M, D)                       # norm1's backward writes the NEXT block's bf16 gradient beside this one's
-            else:
-                ops.gemm_tn_grouped(dw, M)
-            if fused:         # dX of qkv with norm1's backward in its epilogue
-                ops.gemm_ln_bwd(dqkv, f.wt16[p + "attn.qkv.weight"], s["x_in"], s["mean1"], s["rstd1"],
-                                f.w32(p + "norm1.weight"), dres=dx, dx32=dx, dx16=dxa, dgamma=f.g(p + "norm1.weight"),
-                                dbeta=f.g(p + "norm1.bias"), rowscale16=rs_prev, xn16=s["xn1"], beta=f.w32(p + "norm1.bias"))
-            else:
-                ops.gemm_nt(dqkv, f.wt16[p + "attn.qkv.weight"], L.EPI_BIAS_BF16, dxn)
-                ops.layernorm_bwd(s["x_in"], D, s["mean1"], s["rstd1"], f.w32(p + "norm1.weight"), M, dy16=dxn, dres=dx,
-                                  dx32=dx, dx16=dxa, dgamma=f.g(p + "norm1.weight"), dbeta=f.g(p + "norm1.bias"),
-                                  rowscale16=rs_prev)
-            if G > 1:
-                if len(pend_blocks) == G or i == 0:
-                    flush_dw()
-                continue
-            saved["blocks"][i] = None
-            if self.grad_ready_hook:                  # the block's gradient slice is final: DP all-reduce may start
-                self.grad_ready_hook(*self.block_grad_range(i))
-        flush_dw()
-        if pend_extra:                                # (no block below the CLS-only one: depth 1)
-            ops.gemm_tn_grouped(pend_extra, M)
-        dpatch = e16(saved["patches"].shape[0], D)
-        for g in groups:
-            Fr, ntok, lo, po = g["Fr"], g["ntok"], g["off"], g["poff"]
-            dxg, dpg = dx[lo:lo + Fr * ntok], dpatch[po:po + Fr * (ntok - 1)]
+                self._block_bwd_launches(pl, i, s, dx, dxa, dxa_out, t, rs_attn, rs_prev, pend)
+            dxa = dxa_out
+            pend.blocks.append(i)
+            if len(pend.blocks) == G or i == 0:        # (G = 1: nothing is pending, the block is just finished)
+                pend.flush()
+        pend.flush()
+        self._embed_bwd(saved, dx)
+
+    def _final_norm_bwd(self, saved, dreps, dx, dxa):
+        """Backward of the final norm on the CLS rows into the (zeroed) residual-stream gradient, and its bf16 copy."""
+        f = self.flat
+        for g in saved["groups"]:
+            r, fr = g["rows"], g["frames"]
+            ops.layernorm_bwd(saved["x_final"][r], g["ntok"] * D, saved["meanN"][fr], saved["rstdN"][fr], f.w32("norm.weight"),
+                              g["Fr"], dy32=dreps[fr], dx32=dx[r], lddx32=g["ntok"] * D, dgamma=f.g("norm.weight"),
+                              dbeta=f.g("norm.bias"))
+        # with DropPath the gradient that enters a branch is s dx (the residual stream keeps dx): the bf16 copies carry the
+        # NEXT branch's scale — dxa feeds an MLP branch (2i + 1), dxb an attention branch (2i)
+        dp = saved.get("dp")
+        if dp is None:
+            ops.cast_bf16(dx, dxa)
+        else:
+            ops.cast_bf16_rows(dx, dp[2 * (self.depth - 1) + 1], dxa)
+        if self.grad_ready_hook:
+            self.grad_ready_hook(f.offsets["norm.weight"], f.numel)
+
+    def _block_bwd_launches(self, pl, i, s, dx, dxa, dxa_out, t, rs_attn, rs_prev, pend):
+        """One block's backward as its launches; its weight gradients are launched here or left to `pend`."""
+        f, p, M, fused = self.flat, f"blocks.{i}.", pl.M, pl.fused
+        if pl.defer:                                  # this block's gradient tensors are its own
+            t.du, t.dqkv, t.dxb = pl.e16(M, HID), pl.e16(M, 3 * D), pl.e16(M, D)
+        du, dqkv, dxb, dxn, dao = t.du, t.dqkv, t.dxb, t.dxn, t.dao
+        # MLP branch
+        if pl.mlp_fused:                              # dX of fc2 x GELU' -> dX of fc1 -> norm2's backward: ONE launch
+            ops.mlp_bwd(dxa, f.wt16[p + "mlp.fc2.weight"], s["dgelu"], f.wt16[p + "mlp.fc1.weight"], du, s["x_mid"],
+                        s["mean2"], s["rstd2"], f.w32(p + "norm2.weight"), dres=dx, dx32=dx, dx16=dxb,
+                        dgamma=f.g(p + "norm2.weight"), dbeta=f.g(p + "norm2.bias"), rowscale16=rs_attn)
+        elif fused:       # dX of fc1 with norm2's backward (+ residual gradient) in its epilogue
+            ops.gemm_nt(dxa, f.wt16[p + "mlp.fc2.weight"], ops.epi_mul(M), du, aux=s["dgelu"])
+            ops.gemm_ln_bwd(du, f.wt16[p + "mlp.fc1.weight"], s["x_mid"], s["mean2"], s["rstd2"],
+                            f.w32(p + "norm2.weight"), dres=dx, dx32=dx, dx16=dxb, dgamma=f.g(p + "norm2.weight"),
+                            dbeta=f.g(p + "norm2.bias"), rowscale16=rs_attn, xn16=s["xn2"], beta=f.w32(p + "norm2.bias"))
+        else:
+            ops.gemm_nt(dxa, f.wt16[p + "mlp.fc2.weight"], ops.epi_mul(M), du, aux=s["dgelu"])
+            ops.gemm_nt(du, f.wt16[p + "mlp.fc1.weight"], L.EPI_BIAS_BF16, dxn)
+            ops.layernorm_bwd(s["x_mid"], D, s["mean2"], s["rstd2"], f.w32(p + "norm2.weight"), M, dy16=dxn, dres=dx,
+                              dx32=dx, dx16=dxb, dgamma=f.g(p + "norm2.weight"), dbeta=f.g(p + "norm2.bias"),
+                              rowscale16=rs_attn)
+        # attention branch
+        ops.gemm_nt(dxb, f.wt16[p + "attn.proj.weight"], L.EPI_BIAS_BF16, dao)
+        for g, lg in zip(pl.groups, s["lse"]):
+            r = g["rows"]
+            ops.vit_attn_bwd(s["qkv"][r], dao[r], s["ao"][r], lg, None, g["Fr"], dqkv[r], ntok=g["ntok"])
+        # all four weight / bias gradients of the block in one launch.  (A side stream for this launch was measured
+        # in round 1: 20.4 vs 19.6 ms/step — both kernels fill the chip — and removed.)
+        dw = [(dxa, s["h"], f.g(p + "mlp.fc2.weight"), f.g(p + "mlp.fc2.bias")),
+              (du, s["xn2"], f.g(p + "mlp.fc1.weight"), f.g(p + "mlp.fc1.bias")),
+              (dxb, s["ao"], f.g(p + "attn.proj.weight"), f.g(p + "attn.proj.bias")),
+              (dqkv, s["xn1"], f.g(p + "attn.qkv.weight"), f.g(p + "attn.qkv.bias"))]
+        if pl.defer:
+            pend.items += dw
+        else:
+            ops.gemm_tn_grouped(dw, M)
+        if fused:         # dX of qkv with norm1's backward in its epilogue
+            ops.gemm_ln_bwd(dqkv, f.wt16[p + "attn.qkv.weight"], s["x_in"], s["mean1"], s["rstd1"],
+                            f.w32(p + "norm1.weight"), dres=dx, dx32=dx, dx16=dxa_out, dgamma=f.g(p + "norm1.weight"),
+                            dbeta=f.g(p + "norm1.bias"), rowscale16=rs_prev, xn16=s["xn1"], beta=f.w32(p + "norm1.bias"))
+        else:
+            ops.gemm_nt(dqkv, f.wt16[p + "attn.qkv.weight"], L.EPI_BIAS_BF16, dxn)
+            ops.layernorm_bwd(s["x_in"], D, s["mean1"], s["rstd1"], f.w32(p + "norm1.weight"), M, dy16=dxn, dres=dx,
+                              dx32=dx, dx16=dxa_out, dgamma=f.g(p + "norm1.weight"), dbeta=f.g(p + "norm1.bias"),
+                              rowscale16=rs_prev)
+
+    def _embed_bwd(self, saved, dx):
+        """Backward of the embedding per group, then the patch projection's weight gradient over all groups."""
+        f = self.flat
+        dpatch = torch.empty(saved["patches"].shape[0], D, dtype=torch.bfloat16, device=dx.device)
+        for g in saved["groups"]:
+            Fr, ntok = g["Fr"], g["ntok"]
+            dxg, dpg = dx[g["rows"]], dpatch[g["prows"]]
             if g["interp"] is None:
                 ops.vit_embed_bwd(dxg, Fr, f.g("cls_token"), f.g("pos_embed"), dpg)
             else:                                   # through the transpose of the bicubic map (autograd of :174-194)
-                dpos = torch.zeros(ntok, D, dtype=torch.float32, device=dev)
+                dpos = torch.zeros(ntok, D, dtype=torch.float32, device=dx.device)
                 ops.vit_embed_bwd(dxg, Fr, f.g("cls_token"), dpos, dpg, ntok=ntok)
                 ops.pos_interp_bwd(g["interp"], dpos, f.g("pos_embed").view(NTOK, D))
         # (the ping-pong 128 x 384 dW kernel is no better here: 6 wide tiles x 42 row splits, 77 us against 65-68 us)
