@@ -589,7 +589,7 @@ int launch_bwd(const void* qkv, long ldqkv, const void* dout, long lddo, const v
     const int nprob = frames * NH;
 #if SAIS_EXPERIMENTAL
     // SAIS_ATTN_BWD_NB (read once): 1 = the barrier-free form (197 tokens only), 0 = the single-pass kernel with the dS hand-off
-    static const bool nb = [] { const char* e = getenv("SAIS_ATTN_BWD_NB"); return e ? atoi(e) != 0 : SAIS_ATTN_BWD_NB_DEFAULT; }();
+    static const bool nb = sais_env_int("SAIS_ATTN_BWD_NB", SAIS_ATTN_BWD_NB_DEFAULT) != 0;
     if constexpr (G::NKT > 4) {
         if (nb) {
             if (set_lds<NbTag<G>>(attn_bwd_nb_kernel<G>, bwd_nb_lds<G>())) return SAIS_ERR_LAUNCH;

@@ -93,7 +93,7 @@ int dw_nsplit(int M, int nblocks) {
 }  // namespace
 
 extern "C" int sais_gelu_grad_bytes(void) {
-    static const int v = [] { const char* e = getenv("SAIS_GELU_GRAD_Q8"); return (e && atoi(e) == 0) ? 2 : 1; }();
+    static const int v = sais_env_int("SAIS_GELU_GRAD_Q8", 1) == 0 ? 2 : 1;
     return v;
 }
 

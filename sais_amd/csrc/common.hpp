@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 typedef __bf16 bf16;
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
@@ -127,7 +128,7 @@ DEVINL float dgelu_erf(float u) {
     return g.x;
 }
 
-// ---- shared by the GEMM kernels (gemm.hip, gemm_row.hip) --------------------------------------------------------
+// ---- shared by the GEMM kernels (gemm*.hip) --------------------------------------------------------
 // LDS tile image: 128-B rows (64 bf16), 16-B chunk index XOR (row & 7) -> conflict-free ds_read_b128 fragment reads.
 DEVINL int swz(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }
 
@@ -172,6 +173,26 @@ static inline int sais_check_launch() {
     if (e != hipSuccess) sais_set_last_error((int)e);
     return e == hipSuccess ? SAIS_OK : SAIS_ERR_LAUNCH;
 }
+
+// integer environment switch; a site reads it once per process:  static const int v = sais_env_int("SAIS_X", 0);
+static inline int sais_env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+
+// hipFuncAttributeMaxDynamicSharedMemorySize, set once per thread for KERNEL (every kernel and every instantiation of a kernel
+// template is its own instantiation of this function, with its own flag).  false: the runtime refused
+template <auto KERNEL>
+static inline bool sais_dyn_lds_once(int bytes) {
+    static thread_local bool set = false;
+    if (!set) set = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
+    return set;
+}
+
+// -DSAIS_EXPERIMENTAL=1 (tools/build_variant.sh exp -DSAIS_EXPERIMENTAL=1) adds the rejected kernel forms kept as experiment records
+#ifndef SAIS_EXPERIMENTAL
+#define SAIS_EXPERIMENTAL 0
+#endif
 
 // SAIS_CLK_STAMP (diagnostic builds only, tools/clk_probe.py; MI355X_MICROARCH.md "DVFS give-back" item 6): workgroup 0 of a
 // stamped kernel records the shader-clock and the 100-MHz real-time ticks of its own lifetime, so that

@@ -1,0 +1,237 @@
+// sais_gemm_nt_f32: NT with fp32 operands at ~fp32 accuracy on the bf16 matrix cores ("bf16x3"): every operand is split
+// while staging into hi = bf16(x), lo = bf16(x - hi) and the product is accumulated as
+// a_hi b_hi + a_hi b_lo + a_lo b_hi (the dropped lo*lo term is ~2^-18 relative).  Used for the temporal
+// encoder, whose activations feed the <=1e-3 logit parity bar directly and are tiny (M = clips*(T+1)),
+// so 3x the MFMA work is irrelevant.  Single LDS stage (4 x 16 KiB), same swizzle / operand swap /
+// 16-contiguous-columns-per-lane epilogue as the bf16 kernel.
+#include "gemm_nt_tile.hpp"
+#include "philox.hpp"
+
+namespace {
+
+template <int EPI>
+DEVINL void epilogue_f32(const NtParams& p, int m, int n, const float (&v)[16]) {
+    if (p.grp_in > 1) {
+        // split-K: raw partial sums go to the workspace slab of this split; splitk_reduce_kernel applies the epilogue
+        float* o = (float*)p.out2 + ((size_t)blockIdx.z * p.M + m) * p.N + n;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) *(f32x4*)(o + 4 * i) = f32x4{v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]};
+        return;
+    }
+    // four columns at a time (the dropout draws would otherwise push the 64-accumulator kernel into scratch).
+    // Train-mode dropout of the encoder layer, fused: relu -> dropout (FFN), dropout -> + residual (dropout1 / dropout2),
+    // and in the backward drelu -> the same FFN mask.
+    const bool dropping = p.p_drop > 0.f;
+    const unsigned thr = drop_threshold(p.p_drop);
+    const float inv = dropping ? 1.0f / (1.0f - p.p_drop) : 1.0f;
+    float* o = (float*)p.out + (size_t)m * p.ldo + n;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        f32x4 t;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int i = 4 * q + j;
+            t[j] = v[i] + (p.bias ? p.bias[n + i] : 0.f);
+        }
+        f32x4 keep = {1.f, 1.f, 1.f, 1.f};
+        if (dropping) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                keep[j] = philox_keep(p.rng, p.site, (unsigned long long)m * p.N + n + 4 * q + j, thr) ? inv : 0.f;
+        }
+        if constexpr (EPI == SAIS_EPI_BIAS_RELU_F32) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) t[j] = fmaxf(t[j], 0.f) * keep[j];
+        } else if constexpr (EPI == SAIS_EPI_BIAS_RESID_F32) {
+            const f32x4 r = *(const f32x4*)((const float*)p.aux + (size_t)m * p.ldaux + n + 4 * q);
+            t = t * keep + r;
+        } else if constexpr (EPI == SAIS_EPI_DRELU_F32) {
+            const f32x4 u = *(const f32x4*)((const float*)p.aux + (size_t)m * p.ldaux + n + 4 * q);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) t[j] = u[j] > 0.f ? t[j] * keep[j] : 0.f;
+        }
+        *(f32x4*)(o + 4 * q) = t;
+    }
+}
+
+DEVINL void split8(const f32x4& a, const f32x4& b, u32x4& hi, u32x4& lo) {
+    bf16x8 h, l;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        h[i] = (bf16)a[i]; l[i] = (bf16)(a[i] - (float)h[i]);
+        h[4 + i] = (bf16)b[i]; l[4 + i] = (bf16)(b[i] - (float)h[4 + i]);
+    }
+    hi = __builtin_bit_cast(u32x4, h);
+    lo = __builtin_bit_cast(u32x4, l);
+}
+
+template <int EPI>
+__global__ __launch_bounds__(256) void gemm_nt_f32x3_kernel(NtParams p) {
+    __shared__ __attribute__((aligned(16))) char smem[4 * TILE_BYTES];      // A_hi | A_lo | B_hi | B_lo
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int wr = wid >> 1, wc = wid & 1, g = lane >> 4, li = lane & 15;
+    const int n0 = blockIdx.x * BN, m0 = blockIdx.y * BM;
+    const float* A = (const float*)p.A;
+    const float* B = (const float*)p.B;
+    const int sc = tid & 7, sr = tid >> 3;
+    f32x4 ra[4][2], rb[4][2];
+    auto gload = [&](int k0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            int r = sr + 32 * i, m = m0 + r;
+            const float* pa = A + (size_t)(m < p.M ? m : 0) * p.lda + k0 + sc * 8;
+            const float* pb = B + (size_t)(n0 + r) * p.ldb + k0 + sc * 8;
+            bool ok = m < p.M;
+            ra[i][0] = ok ? *(const f32x4*)pa : f32x4{0, 0, 0, 0};
+            ra[i][1] = ok ? *(const f32x4*)(pa + 4) : f32x4{0, 0, 0, 0};
+            rb[i][0] = *(const f32x4*)pb;
+            rb[i][1] = *(const f32x4*)(pb + 4);
+        }
+    };
+    auto lstore = [&]() {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            int r = sr + 32 * i;
+            u32x4 hi, lo;
+            split8(ra[i][0], ra[i][1], hi, lo);
+            *(u32x4*)(smem + swz(r, sc)) = hi;
+            *(u32x4*)(smem + TILE_BYTES + swz(r, sc)) = lo;
+            split8(rb[i][0], rb[i][1], hi, lo);
+            *(u32x4*)(smem + 2 * TILE_BYTES + swz(perm_row(r), sc)) = hi;
+            *(u32x4*)(smem + 3 * TILE_BYTES + swz(perm_row(r), sc)) = lo;
+        }
+    };
+    f32x4 acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0, 0, 0, 0};
+    // split-K: grp_in = number of K splits (gridDim.z); this workgroup owns K-tiles [kbeg, kbeg + nk)
+    const int nk = p.K / BK / (p.grp_in > 1 ? p.grp_in : 1);
+    const int kbeg = blockIdx.z * nk;
+    gload(kbeg * BK);
+    for (int kt = 0; kt < nk; ++kt) {
+        __syncthreads();                       // previous tile fully consumed
+        lstore();
+        __syncthreads();
+        if (kt + 1 < nk) gload((kbeg + kt + 1) * BK);
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            bf16x8 ah[4], al[4], bh[4], bl[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                int oa = swz(wr * 64 + t * 16 + li, ks * 4 + g), ob = swz(wc * 64 + t * 16 + li, ks * 4 + g);
+                ah[t] = *(const bf16x8*)(smem + oa);
+                al[t] = *(const bf16x8*)(smem + TILE_BYTES + oa);
+                bh[t] = *(const bf16x8*)(smem + 2 * TILE_BYTES + ob);
+                bl[t] = *(const bf16x8*)(smem + 3 * TILE_BYTES + ob);
+            }
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt) {
+                    f32x4 c = acc[mt][nt];
+                    c = mfma16(bl[nt], ah[mt], c);
+                    c = mfma16(bh[nt], al[mt], c);
+                    c = mfma16(bh[nt], ah[mt], c);
+                    acc[mt][nt] = c;
+                }
+        }
+    }
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+        int m = m0 + wr * 64 + mt * 16 + li;
+        if (m >= p.M) continue;
+        float v[16];
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[4 * nt + r] = acc[mt][nt][r];
+        epilogue_f32<EPI>(p, m, n0 + wc * 64 + 16 * g, v);
+    }
+}
+
+}  // namespace
+
+// out[m][n] = epilogue( sum_z ws[z][m][n] + bias[n] , aux[m][n] )  — second half of the split-K fp32 GEMM
+template <int EPI>
+__global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* ws, int ks, int M, int N, const float* bias,
+                                                            const float* aux, int ldaux, float* out, int ldo, float p_drop,
+                                                            const unsigned long long* rng, unsigned site) {
+    const int n4 = N >> 2;
+    const unsigned thr = drop_threshold(p_drop);
+    const float inv = p_drop > 0.f ? 1.0f / (1.0f - p_drop) : 1.0f;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < (long)M * n4; i += (long)gridDim.x * 256) {
+        const int m = i / n4, n = (i - (long)m * n4) * 4;
+        f32x4 y = *(const f32x4*)(ws + (size_t)m * N + n);
+        for (int z = 1; z < ks; ++z) y += *(const f32x4*)(ws + ((size_t)z * M + m) * N + n);
+        if (bias) y += *(const f32x4*)(bias + n);
+        f32x4 keep = {1.f, 1.f, 1.f, 1.f};
+        if (p_drop > 0.f) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) keep[j] = philox_keep(rng, site, (unsigned long long)m * N + n + j, thr) ? inv : 0.f;
+        }
+        if constexpr (EPI == SAIS_EPI_BIAS_RESID_F32) y = y * keep + *(const f32x4*)(aux + (size_t)m * ldaux + n);
+        if constexpr (EPI == SAIS_EPI_BIAS_RELU_F32) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) y[j] = fmaxf(y[j], 0.f) * keep[j];
+        }
+        if constexpr (EPI == SAIS_EPI_DRELU_F32) {
+            const f32x4 u = *(const f32x4*)(aux + (size_t)m * ldaux + n);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) y[j] = u[j] > 0.f ? y[j] * keep[j] : 0.f;
+        }
+        *(f32x4*)(out + (size_t)m * ldo + n) = y;
+    }
+}
+
+#define LAUNCH_RED(E)                                                                                             \
+    case E:                                                                                                       \
+        hipLaunchKernelGGL(splitk_reduce_kernel<E>, dim3(rgrid), dim3(256), 0, (hipStream_t)stream,              \
+                           (const float*)g->out2, ks, g->M, g->N, g->bias, (const float*)g->aux, g->ldaux,        \
+                           (float*)g->out, g->ldo, g->p_drop, g->rng_state, g->site);                             \
+        break;
+
+#define LAUNCH_NT32(E)                                                                            \
+    case E:                                                                                       \
+        hipLaunchKernelGGL(gemm_nt_f32x3_kernel<E>, grid, dim3(256), 0, (hipStream_t)stream, p);  \
+        break;
+
+extern "C" int sais_gemm_nt_f32(const SaisGemm* g, void* stream) {
+    SAIS_ENTER();
+    if (!g || !g->A || !g->B || !g->out) return SAIS_ERR_ARG;
+    if (g->M <= 0 || g->N % BN || g->K % BK || g->lda % 4 || g->ldb % 4 || g->ldo % 4) return SAIS_ERR_ARG;
+    NtParams p{(const bf16*)g->A, (const bf16*)g->B, g->lda, g->ldb, g->M, g->N, g->K, g->bias,
+               g->out, g->ldo, g->out2, g->ldo2, g->aux, g->ldaux, 1, 0, 0, nullptr, g->p_drop, g->rng_state, g->site};
+    if (g->p_drop < 0.f || g->p_drop >= 1.f || (g->p_drop > 0.f && (!g->rng_state || g->epilogue == SAIS_EPI_BIAS_F32)))
+        return SAIS_ERR_ARG;
+    dim3 grid(g->N / BN, (g->M + BM - 1) / BM);
+    // Few output tiles (M = clips*(T+1) rows): split K over gridDim.z into the caller's workspace (out2 = f32
+    // [ldo2][M][N], ldo2 = number of splits) and finish with a tiny reduce+epilogue kernel, so that dozens of CUs
+    // work instead of <= 9 and the exposed per-K-tile load latency is paid K/64/ks times instead of K/64.
+    int ks = 1;
+    if (g->out2 && g->ldo2 > 1) {
+        ks = g->ldo2;
+        if ((g->K / BK) % ks) return SAIS_ERR_ARG;
+        p.grp_in = ks;
+        grid.z = ks;
+    }
+    switch (g->epilogue) {
+        LAUNCH_NT32(SAIS_EPI_BIAS_F32)
+        LAUNCH_NT32(SAIS_EPI_BIAS_RESID_F32)
+        LAUNCH_NT32(SAIS_EPI_BIAS_RELU_F32)
+        LAUNCH_NT32(SAIS_EPI_DRELU_F32)
+        default: return SAIS_ERR_ARG;
+    }
+    if (ks > 1) {
+        long n = (long)g->M * (g->N / 4);
+        int rgrid = (int)((n + 255) / 256);
+        switch (g->epilogue) {
+            LAUNCH_RED(SAIS_EPI_BIAS_F32)
+            LAUNCH_RED(SAIS_EPI_BIAS_RESID_F32)
+            LAUNCH_RED(SAIS_EPI_BIAS_RELU_F32)
+            LAUNCH_RED(SAIS_EPI_DRELU_F32)
+        }
+    }
+    return sais_check_launch();
+}

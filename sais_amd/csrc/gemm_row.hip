@@ -277,7 +277,7 @@ int rows_per_tile(int M) {
     int rows = (M + slots * rounds - 1) / (slots * rounds);
     // few rows per workgroup waste MFMA row tiles (all RMT are always computed); many-row tiles leave workgroup slots
     // empty.  SAIS_ROW_MINROWS overrides the switch-over for A/B measurements.
-    static const int minrows = [] { const char* e = getenv("SAIS_ROW_MINROWS"); return e ? atoi(e) : 0; }();
+    static const int minrows = sais_env_int("SAIS_ROW_MINROWS", 0);
     if (rows < (minrows > 0 ? minrows : cap / 2 + 8)) rows = cap;
     return rows;
 }
@@ -285,7 +285,7 @@ int rows_per_tile(int M) {
 // the eight-wave tile pays when a launch fills the chip with whole 1-workgroup-per-CU rounds: the ViT GEMMs of a training
 // step and of large extraction batches.  SAIS_ROW_WAVES=4 / 8 forces one form (A/B measurements).
 bool use_eight_waves(int M) {
-    static const int forced = [] { const char* e = getenv("SAIS_ROW_WAVES"); return e ? atoi(e) : 0; }();
+    static const int forced = sais_env_int("SAIS_ROW_WAVES", 0);
     if (forced == 4) return false;
     if (forced == 8) return true;
     return M >= 256 * 112;
@@ -293,14 +293,7 @@ bool use_eight_waves(int M) {
 
 template <int EPI, bool DP, int NW, bool STAG = false, bool SPEC = false>
 int launch_row_nw(RowParams& p, void* stream) {
-    static thread_local bool set = false;
-    if (!set) {
-        constexpr int lds_max = row_lds<NW, SPEC>();
-        if (hipFuncSetAttribute((const void*)gemm_nt_row_kernel<EPI, DP, NW, STAG, SPEC>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                lds_max) != hipSuccess)
-            return SAIS_ERR_LAUNCH;
-        set = true;
-    }
+    if (!sais_dyn_lds_once<gemm_nt_row_kernel<EPI, DP, NW, STAG, SPEC>>(row_lds<NW, SPEC>())) return SAIS_ERR_LAUNCH;
     // 32-bit byte offsets inside the kernel
     if ((double)p.M * p.lda * 2.0 >= 4294967296.0 || (double)p.N * p.ldw * 2.0 >= 4294967296.0) return SAIS_ERR_ARG;
     p.rows_per_tile = rows_per_tile<NW>(p.M);
@@ -312,9 +305,9 @@ int launch_row_nw(RowParams& p, void* stream) {
 
 template <int EPI, bool DP>
 int launch_row_dp(RowParams& p, void* stream) {
-    static const bool stag = [] { const char* e = getenv("SAIS_ROW_STAG"); return e ? atoi(e) != 0 : true; }();
+    static const bool stag = sais_env_int("SAIS_ROW_STAG", 1) != 0;
     if (!use_eight_waves(p.M)) return launch_row_nw<EPI, DP, 4>(p, stream);
-    static const bool spec = [] { const char* e = getenv("SAIS_ROW_SPEC"); return e ? atoi(e) != 0 : true; }();
+    static const bool spec = sais_env_int("SAIS_ROW_SPEC", 1) != 0;
     if (spec) return stag ? launch_row_nw<EPI, DP, 8, true, true>(p, stream) : launch_row_nw<EPI, DP, 8, false, true>(p, stream);
     return stag ? launch_row_nw<EPI, DP, 8, true>(p, stream) : launch_row_nw<EPI, DP, 8, false>(p, stream);
 }
@@ -373,7 +366,7 @@ extern "C" int sais_gemm_ln_bwd(const SaisGemmLn* g, void* stream) {
     p.gamma = g->gamma; p.mean = g->mean; p.rstd = g->rstd;
     p.dres = g->dres; p.lddres = g->lddres; p.dres_period = g->dres_period; p.dgamma = g->dgamma; p.dbeta = g->dbeta;
     p.rowscale = g->rowscale16;
-    static const bool x16 = [] { const char* e = getenv("SAIS_LN_BWD_X16"); return e ? atoi(e) != 0 : true; }();
+    static const bool x16 = sais_env_int("SAIS_LN_BWD_X16", 1) != 0;
     if (x16 && g->xn16 && g->beta) {
         if ((g->ldxn16 & 3) || ((uintptr_t)g->xn16 & 7)) return SAIS_ERR_ARG;
         p.xn16 = (const bf16*)g->xn16; p.ldxn16 = g->ldxn16; p.beta = g->beta;

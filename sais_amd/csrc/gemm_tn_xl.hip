@@ -1,6 +1,6 @@
 // Large-tile weight-gradient GEMM (round 6): dW[N1,N2] += sum_m P[m,N1] Q[m,N2], db[N1] += colsum(P), bf16 operands.
 //
-// Why another dW kernel.  The 128 x 384 ping-pong kernel of gemm.hip is paced by bytes through the per-CU vector L1 (LABNOTES
+// Why another dW kernel.  The 128 x 384 ping-pong kernel of gemm_tn.hip is paced by bytes through the per-CU vector L1 (LABNOTES
 // R5.5-R5.7: 1.78 GB of LDS fills per launch for 627 MB of unique operands, 16.6 B/clk per CU, TCP stalled on L2 data 62 % of
 // its cycles), and five re-schedulings of that tile changed nothing.  This kernel changes the bytes per flop instead:
 //
@@ -61,9 +61,6 @@ template <int N> DEVINL void xl_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :
 // SAIS_XL_ABL (timing ablations, WRONG results): 1 no LDS-DMA, 2 no MFMAs, 4 no fragment reads, 8 no atomics
 #ifndef SAIS_XL_ABL
 #define SAIS_XL_ABL 0
-#endif
-#ifndef SAIS_EXPERIMENTAL
-#define SAIS_EXPERIMENTAL 0
 #endif
 
 // SLAB: instead of fp32 atomics (75 MB per ViT block at 10 splits: ~50 us of the launch, LABNOTES R6.1: the chip retires ~1.5 TB/s
@@ -471,12 +468,7 @@ extern "C" size_t sais_gemm_tn_xl_slab_bytes_(const SaisTnItem* items, int nitem
 
 template <int NW, bool SLAB>
 static int xl_launch(const XlGroup& gp, float* slabs, hipStream_t stream) {
-    static thread_local bool set = false;
-    if (!set) {
-        if (hipFuncSetAttribute((const void*)gemm_tn_xl_kernel<NW, SLAB>, hipFuncAttributeMaxDynamicSharedMemorySize, XLDS) != hipSuccess)
-            return SAIS_ERR_LAUNCH;
-        set = true;
-    }
+    if (!sais_dyn_lds_once<gemm_tn_xl_kernel<NW, SLAB>>(XLDS)) return SAIS_ERR_LAUNCH;
     const int nwg = gp.ntiles * gp.nsplit;
     hipLaunchKernelGGL((gemm_tn_xl_kernel<NW, SLAB>), dim3(nwg), dim3(64 * NW), XLDS, stream, gp, slabs);
     if constexpr (SLAB) {

@@ -287,13 +287,7 @@ int mlp_rows_per_tile(int M) {
 
 template <int MODE, int EPI, bool DP>
 int launch_mlp(MlpParams& q, void* stream) {
-    static thread_local bool set = false;
-    if (!set) {
-        if (hipFuncSetAttribute((const void*)mlp_fused_kernel<MODE, EPI, DP>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                MLP_LDS) != hipSuccess)
-            return SAIS_ERR_LAUNCH;
-        set = true;
-    }
+    if (!sais_dyn_lds_once<mlp_fused_kernel<MODE, EPI, DP>>(MLP_LDS)) return SAIS_ERR_LAUNCH;
     q.r.rows_per_tile = mlp_rows_per_tile(q.r.M);
     const int grid = (q.r.M + q.r.rows_per_tile - 1) / q.r.rows_per_tile;
     hipLaunchKernelGGL((mlp_fused_kernel<MODE, EPI, DP>), dim3(grid), dim3(256), MLP_LDS, (hipStream_t)stream, q);

@@ -3,7 +3,7 @@
 // convolutions.  PARITY UNPINNED: ptlflow 0.2.5 is absent from the reference tree and from this image; the arithmetic follows
 // the published model and is tested against oracle/raft_oracle.py (see its header).
 //
-//   all-pairs correlation  C[i, j] = <f1[:, i], f2[:, j]> / sqrt(256): sais_gemm_nt_f32 (gemm.hip: fp32 operands split into
+//   all-pairs correlation  C[i, j] = <f1[:, i], f2[:, j]> / sqrt(256): sais_gemm_nt_f32 (gemm_nt_f32.hip: fp32 operands split into
 //       bf16 hi / lo on the matrix cores, fp32-grade) on [H W, 256] feature matrices, one launch per frame pair;
 //   sais_raft_corr_pool    the three coarser pyramid levels (2 x 2 average pooling over the LAST two dims of
 //       [H W, 1, H, W]) from level 0 in ONE pass: a workgroup stages one correlation row (an H x W image, 32 KB at 540 x 960

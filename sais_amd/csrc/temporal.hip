@@ -1,7 +1,7 @@
 // Temporal encoder glue + SupCon / prototype head of SAIS for gfx950.  These tensors are tiny
 // (S = T+1 <= 97 tokens per clip, 4 heads x 96), latency-bound, and feed the <=1e-3 logit parity
 // budget directly, so everything here is exact fp32 VALU math staged through LDS; the linear layers
-// around them go through the MFMA GEMMs in gemm.hip.
+// around them go through the MFMA GEMMs in gemm_nt_f32.hip / gemm_tn.hip.
 //
 //   prepareInputForTransformer  prepare_model.py:179-195   (sais_temporal_prepare_*)
 //   (the attention core: tattn.hip; the linear layers and LayerNorms: tgemm.hip)

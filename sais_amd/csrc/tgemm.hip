@@ -2,7 +2,7 @@
 //
 // The problem: M = clips x (T + 1) is a few hundred rows (264 at the benchmark), N, K in {384, 1152, 2048}: every GEMM is
 // a few GFLOP and a few MB of fp32 weights, i.e. a LATENCY problem — what matters is how many CUs pull on the weights at
-// once and how many dependent round trips a workgroup makes.  Round 2 ran these on the 128 x 128 tile of gemm.hip
+// once and how many dependent round trips a workgroup makes.  Round 2 ran these on the 128 x 128 tile of gemm_nt_f32.hip
 // (48 workgroups for the FFN, one K-step of latency exposed per step: 33 us for 1.2 GFLOP) plus a split-K reduce kernel
 // and a LayerNorm kernel behind every N = 384 GEMM (~110 launches per step).  Here:
 //

@@ -18,7 +18,7 @@ from sais_amd import _lib as L  # noqa: E402
 from sais_amd.graph import GraphedStep  # noqa: E402
 from sais_amd.parallel import GradSync  # noqa: E402
 
-NAMES = {("gemm", 0): "w8p qkv / plain", ("gemm", 1): "w8p fc1 + GELU / GELU'", ("gemm", 2): "w8p dX fc2 x GELU'", ("gemm", 3): "dW (tn_pp)",
+NAMES = {("gemm", 0): "w8p qkv / plain", ("gemm", 1): "w8p fc1 + GELU / GELU'", ("gemm", 2): "w8p dX fc2 x GELU'", ("gemm_tn", 3): "dW (tn_pp)",
          ("row", 4): "row LN_FWD K384 (proj)", ("row", 5): "row LN_FWD K1536 (fc2)", ("row", 6): "row LN_BWD K1152 (dX qkv)",
          ("row", 7): "row LN_BWD K1536 (dX fc1)", ("row", 8): "row plain K384 (dX proj)", ("row", 9): "row plain K1536",
          ("attn", 10): "attention fwd", ("attn", 11): "attention bwd"}
@@ -43,7 +43,7 @@ while time.perf_counter() - t0 < secs:
     torch.cuda.synchronize(); n += 10
 print(f"{n} steps in {time.perf_counter() - t0:.2f} s = {(time.perf_counter() - t0) / n * 1e3:.3f} ms/step (zero input: {zero})")
 lib = L.load()
-for f in ("gemm", "row", "attn"):
+for f in ("gemm", "gemm_tn", "row", "attn"):
     buf = (ctypes.c_ulonglong * 32)()
     fn = getattr(lib, "sais_debug_clk_" + f)
     fn.argtypes = [ctypes.c_void_p]

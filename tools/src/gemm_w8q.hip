@@ -2,8 +2,8 @@
 // tests/test_kernels_gpu.py and the bench line's parity gate when wired into sais_gemm_nt behind SAIS_NT_W8Q=1: dispatch
 // `gemm_nt_w8q_kernel<E><<<min(ntiles, 768), 512, 6 * QSLOT>>>(p, ntiles)` for M >= 8192, K % 32 == 0) and SLOWER than the
 // two-workgroups-per-CU kernel it was meant to beat: fc1 + GELU + GELU' 162-165 vs 140-142 us, dX fc2 x GELU' 150-151 vs
-// 117-118, qkv 71-72 vs 60-62 stand-alone; 13.49-13.55 vs 12.76 ms per step.  It belongs inside gemm.hip's anonymous namespace
-// (NtParams, BM, BN, glds16, perm_row32, xcd_remap, mfma16, epilogue_loads8 / epilogue8).
+// 117-118, qkv 71-72 vs 60-62 stand-alone; 13.49-13.55 vs 12.76 ms per step.  It belongs inside an anonymous namespace
+// after gemm_nt_tile.hpp (NtParams, BM, BN, glds16, perm_row32, xcd_remap, mfma16, epilogue_loads8 / epilogue8), like gemm_nt_exp.hip.
 // ---------------------------------------------------------------------------------------------
 // Three workgroups per CU (experiment, R4.4: a workgroup's K loop is a latency chain and two chains per CU fill neither the
 // LDS / MFMA side nor HBM).  The same 128 x 128 tile, eight waves of 64 x 32, weight-row permutation and epilogue as

@@ -187,7 +187,7 @@ int launch_wstat(const NtParams& p, void* stream) {
 
 }  // namespace
 
-// called by sais_gemm_nt (gemm.hip) for M >= 8192, K in {256, 320, 384}, N >= 1152 (N % 128 == 0, at most 256 panels)
+// called by sais_gemm_nt (gemm.hip; one internal entry, like sais_gemm_nt_exp_ of gemm_nt_exp.hip) for M >= 8192, K in {256, 320, 384}, N >= 1152 (N % 128 == 0, at most 256 panels)
 extern "C" int sais_gemm_nt_wstat_(const SaisGemm* g, void* stream) {
     const int nk = g->K / 64;
     if (g->K % 64 || nk < 4 || nk > 6 || g->N % 128 || g->N / 128 > 256) return SAIS_ERR_ARG;
