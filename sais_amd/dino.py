@@ -25,7 +25,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops
-from .flat import FlatParams
+from .flat import ensure_flat
 from .vit import VisionTransformer, _trunc_normal_, vit_small
 
 F32 = torch.float32
@@ -86,29 +86,20 @@ class DINOHead(nn.Module):
         if norm_last_layer:
             self.last_layer.weight_g.requires_grad = False
         self.flat = None
-        self._sig = None
         self._t_names = ["mlp.0.weight", "mlp.2.weight", "mlp.4.weight"]
-        self._sentinels = ["mlp.0.weight", "mlp.4.bias", "last_layer.weight_v"]
         self._what = None                                            # normalised last-layer weight of the current params
 
     def _engine(self, device):
-        if self.flat is None or not self.flat.intact() or self.flat.device != device:
-            self.flat = FlatParams(self, device, f32_transposes=True)
-            self._sig = None
-        sig = self.flat.signature(self._sentinels)
-        if sig != self._sig:
-            self.flat.refresh_shadows(self._t_names)
+        ensure_flat(self, device, f32_transposes=True, transposed=self._t_names,
+                    sentinels=("mlp.0.weight", "mlp.4.bias", "last_layer.weight_v"))
+        if self.flat.fresh():
             self._refresh_last_layer()
-            self._sig = self.flat.signature(self._sentinels)
         return self.flat
 
-    def shadows_dirty(self):
-        self._sig = None
-
     def load_state_dict(self, *a, **k):
-        r = super().load_state_dict(*a, **k)
-        self._sig = None
-        return r
+        if self.flat is not None:
+            self.flat.mark_dirty()
+        return super().load_state_dict(*a, **k)
 
     def _refresh_last_layer(self, need_backward=True):
         """w = g v / ||v||, its transpose (dX) and its bf16x3 image [hi | lo | hi] (the logits GEMM), once per parameter
@@ -126,11 +117,8 @@ class DINOHead(nn.Module):
         ops.split_bf16x3(w, w3, True)
 
     def after_optimizer_step(self, need_backward=True):
-        if need_backward:
-            self.flat._transposes(self._t_names)
-        self.flat.epoch += 1
+        self.flat.stepped(transposes=need_backward)
         self._refresh_last_layer(need_backward)
-        self._sig = self.flat.signature(self._sentinels)
 
     def forward(self, x):
         return self.forward_kernels(x, save=False)[0]
@@ -413,14 +401,9 @@ class DINOOptimizer:
         for part, shadow in self._parts:
             part.step(clip_grad, lr, wd, self.betas, self.eps, self.steps, frozen_last_layer,
                       1.0 if ema_momentum is None else ema_momentum, shadow, self.grad_scale)
-        for mod in (self.student, self.teacher):
-            if mod is None:
-                continue
-            bb, trains = mod.backbone, mod is self.student
-            if trains:                                   # the teacher only runs forward: no transposed shadows
-                bb.flat._transposes(bb._t_names)
-            bb.flat.epoch += 1
-            bb._sig = bb.flat.signature(bb._sentinels)
+        for mod in filter(None, (self.student, self.teacher)):
+            trains = mod is self.student                 # the teacher only runs forward: no transposed shadows
+            mod.backbone.flat.stepped(transposes=trains)
             mod.head.after_optimizer_step(need_backward=trains)
 
     # torch.optim.AdamW-compatible checkpoint (main_dino.py:485-491: 'optimizer': optimizer.state_dict())

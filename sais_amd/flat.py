@@ -12,9 +12,14 @@ from . import ops
 
 
 class FlatParams:
-    def __init__(self, module, device, f32_transposes=False):
+    """`transposed`: the weights that get a pre-transposed shadow; `sentinels`: the few parameters whose version counters stand for
+    "edited in place".  Whether the shadows are fresh is decided here alone: fresh / mark_dirty / stepped / weights_key."""
+
+    def __init__(self, module, device, f32_transposes=False, transposed=(), sentinels=()):
         self.module = module
         self.f32_transposes = f32_transposes             # temporal engine: fp32 W^T for the bf16x3 GEMMs
+        self.transposed, self.sentinels = tuple(transposed), tuple(sentinels)
+        self._sig = None                                 # signature() at the last refresh; None = refresh at the next fresh()
         self.device = torch.device(device)
         named = [(n, p) for n, p in module.named_parameters()]
         self.names = [n for n, _ in named]
@@ -83,8 +88,30 @@ class FlatParams:
         return reset
 
     # -- bf16 shadows -----------------------------------------------------------------------
-    def signature(self, sentinels):
-        return (self.epoch,) + tuple(self.params[self._idx[n]]._version for n in sentinels)
+    def signature(self):
+        return (self.epoch,) + tuple(self.params[self._idx[n]]._version for n in self.sentinels)
+
+    def fresh(self):
+        """Refresh the shadows if the parameters moved since the last refresh; returns whether it did."""
+        if self._sig == self.signature():
+            return False
+        self.refresh_shadows(self.transposed)
+        self._sig = self.signature()
+        return True
+
+    def mark_dirty(self):
+        self._sig = None
+
+    def stepped(self, transposes=True):
+        """An optimizer kernel has just rewritten the parameters and the bf16 shadow: only the transposes are left to redo."""
+        if transposes:
+            self._transposes(self.transposed)
+        self.epoch += 1
+        self._sig = self.signature()
+
+    def weights_key(self):
+        """Key for graph caches: a captured graph holds pointers into the shadows and the values of one refresh."""
+        return (self.signature(), self.flat.data_ptr())
 
     def _transposes(self, names):
         """Refresh every transposed shadow in one launch; the descriptor table lives on the device and is rebuilt only
@@ -114,7 +141,14 @@ class FlatParams:
             ops.cast_bf16(self.flat, self.w16)
         self._transposes(transposed_names)
 
-    def sgd_step(self, lr, grad_scale=1.0, transposed_names=()):
+    def sgd_step(self, lr, grad_scale=1.0):
         ops.sgd_step(self.flat, self.grad, None if self.f32_transposes else self.w16, lr, grad_scale)
-        self._transposes(transposed_names)
-        self.epoch += 1
+        self.stepped()
+
+
+def ensure_flat(module, device, **kw):
+    """Build module.flat if it is missing, no longer what the parameters view, or on another device; returns whether it did."""
+    fl = module.flat
+    if fl is None or not fl.intact() or fl.device != device:
+        module.flat = FlatParams(module, device, **kw)
+    return module.flat is not fl

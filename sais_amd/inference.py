@@ -152,7 +152,7 @@ class FeatureExtractor:
         self.tail = tail_batch if (not self.fit and tail_batch and tail_batch < batch_size) else None
         self.use_graph = use_graph
         self._graphs = {}                                             # frames per replay -> (graph, static_in, static_out)
-        self._sig = None
+        self._key = None                                              # the weights the graphs were captured against
 
     def shape_for(self, left):
         """Frames per forward pass for `left` remaining frames: the padded shape, the same for replayed and eager passes."""
@@ -178,13 +178,7 @@ class FeatureExtractor:
             old = next(k for k in self._graphs if k != self.bs)
             del self._graphs[old]
         self._graphs[bs] = (graph, static_in, static_out)
-        self._sig = self._weights_sig(device)
-
-    def _weights_sig(self, device):
-        """The captured launches hold pointers into the ViT's weight shadows and were recorded against one set of weights: a later
-        load_state_dict / optimizer step (FlatParams.signature) or a reallocated flat buffer makes every captured graph stale."""
-        fl = self.vit._engine(device)
-        return (fl.signature(self.vit._sentinels), fl.flat.data_ptr())
+        self._key = self.vit._engine(device).weights_key()
 
     # the attributes older callers / tests read: the main shape's graph
     @property
@@ -204,8 +198,10 @@ class FeatureExtractor:
             bs = self.shape_for(left)
             n = min(bs, left)
             if self.use_graph:
-                if self._graphs and self._weights_sig(frames.device) != self._sig:
-                    self._graphs.clear()                              # the weights changed since the capture: never replay those
+                # the captured launches hold pointers into the ViT's weight shadows and were recorded against one set of weights: a
+                # load_state_dict / optimizer step or a reallocated flat buffer since then makes every captured graph stale
+                if self._graphs and self.vit._engine(frames.device).weights_key() != self._key:
+                    self._graphs.clear()
                 if bs not in self._graphs:
                     self._capture(frames.device, bs)
                 graph, static_in, static_out = self._graphs[bs] = self._graphs.pop(bs)      # re-insert: most recently used last
@@ -337,10 +333,8 @@ def run_windows(model, rgb_reps, flow_reps, videoname="video", batch_size=2, tot
         # a wider compute chunk would change the shape the reference saves for a batch whose windows all have one flow row
         cb, use_graph = batch_size, False
     emb_parts, attn_parts, imp_parts = ([], [], []), [], []
-    from . import temporal as _tmod
-    fast = (not use_graph and _tmod._TTA_MERGE and hasattr(model, "_tta_core") and model.modalities == "RGB-Flow"
-            and not model.importance_loss and '+' not in getattr(model, "domain", "")
-            and all(e - s == DURATION_FRAMES for s, e in mine))
+    merged_ok = getattr(model, "merged_pass_ok", None)           # fullModel's own answer; a stand-in model has none
+    fast = not use_graph and merged_ok is not None and merged_ok(stacked=True) and all(e - s == DURATION_FRAMES for s, e in mine)
     for i in range(0, len(mine), cb):
         chunk = mine[i:i + cb]
         n = len(chunk)
@@ -348,9 +342,9 @@ def run_windows(model, rgb_reps, flow_reps, videoname="video", batch_size=2, tot
             c = collate_windows_tta(rgb_reps, flow_reps, chunk + [chunk[-1]] * (cb - n), pad_flow_to=_WindowGraph.FLOW_PAD)
             graphs = model.__dict__.setdefault("_window_graphs", {})
             # the captured launches hold pointers into the model's weight shadows: a graph is valid only for the weights it was captured
-            # with (FlatParams.signature changes on load_state_dict / an optimizer step, and shadows may then be reallocated)
-            sig = model._engine(rgb_reps.device).signature(model._sentinels())
-            key = (cb, str(rgb_reps.device), tuple(tuple(t.shape) for t in c["x"] + c["f"]), sig, model.flat.flat.data_ptr())
+            # with (the key changes on load_state_dict / an optimizer step / a reallocated buffer)
+            key = (cb, str(rgb_reps.device), tuple(tuple(t.shape) for t in c["x"] + c["f"])) + \
+                model._engine(rgb_reps.device).weights_key()
             for k in [k for k in graphs if k[:3] == key[:3] and k != key]:
                 del graphs[k]                                    # stale weights: drop, never replay
             if key not in graphs:

@@ -20,6 +20,26 @@ def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _drop3(drop, site=None):
+    """Kernel arguments (p, rng, site) of drop = (p, rng_state[, site]) | None; `site`: passed whether dropout is on or not."""
+    p, rng, s = (0.0, None, 0) if drop is None else (tuple(drop) + (0,))[:3]
+    return float(p), _p(rng), int(s if site is None else site)
+
+
+def _slabs3(slabs):
+    return (None, 0, 0) if slabs is None else (_p(slabs), slabs.shape[0], slabs.stride(0))
+
+
+def _tn_item(p, q, dW, db):
+    return L.SaisTnItem(_p(p), p.stride(0), _p(q), q.stride(0), p.shape[1], q.shape[1], _p(dW), dW.stride(0), _p(db))
+
+
+def _tn_nsplit(nsplit, M, tiles):
+    """The caller's M-split of a dW launch, or the default.  Measured sweep on MI355X (tools/gemm_bench.py): ~430 workgroups is the
+    sweet spot between chip fill (2 workgroups/CU) and fp32-atomic traffic (64 KiB per workgroup)."""
+    return max(1, min((M + 255) // 256, (432 + tiles - 1) // tiles)) if nsplit is None else nsplit
+
+
 class KernelTimer:
     """Optional live per-kernel timing with HIP events on the launch stream (used by bench.py for the
     roofline object).  tag -> [(start, end, algorithmic flops, algorithmic bytes)]."""
@@ -233,9 +253,7 @@ def gemm_nt_f32(a, w, epilogue, out, bias=None, aux=None, M=None, drop=None):
         ws = torch.empty(ks, M, N, dtype=F32, device=a.device)
     g = L.SaisGemm(_p(a), a.stride(0), _p(w), w.stride(0), M, N, K, epilogue, _p(bias),
                    _p(out), out.stride(-2), _p(ws), ks if ws is not None else 0, _p(aux),
-                   0 if aux is None else aux.stride(-2), 0, 0, 0, None,
-                   0.0 if drop is None else float(drop[0]), None if drop is None else _p(drop[1]),
-                   0 if drop is None else int(drop[2]))
+                   0 if aux is None else aux.stride(-2), 0, 0, 0, None, *_drop3(drop))
     _timed(f"gemm_nt_f32x3<{_NT_NAMES[epilogue]}>", 2.0 * M * N * K, 4 * (M * K + N * K + M * N),
            lambda: L.call("sais_gemm_nt_f32", ctypes.byref(g), _stream()))
     return out
@@ -249,9 +267,7 @@ def tgemm(a, w, epilogue, out, bias=None, aux=None, nsplit=1, drop=None):
     M, K = a.shape
     N = w.shape[0]
     g = L.SaisTGemm(_p(a), a.stride(0), _p(w), w.stride(0), M, N, K, epilogue, nsplit, _p(bias), _p(aux),
-                    0 if aux is None else aux.stride(0), _p(out), out.stride(-2),
-                    0.0 if drop is None else float(drop[0]), None if drop is None else _p(drop[1]),
-                    0 if drop is None else int(drop[2]))
+                    0 if aux is None else aux.stride(0), _p(out), out.stride(-2), *_drop3(drop))
     _timed("tgemm", 2.0 * M * N * K, 4 * (M * K + N * K + M * N), lambda: L.call("sais_tgemm", ctypes.byref(g), _stream()))
     return out
 
@@ -259,19 +275,15 @@ def tgemm(a, w, epilogue, out, bias=None, aux=None, nsplit=1, drop=None):
 def temporal_ln_fwd(slabs, bias, resid, gamma, beta, eps, z, y=None, mean=None, rstd=None, drop=None):
     """y = resid + drop(sum_z slabs[z] + bias) ; z = LayerNorm(y).  slabs f32 [nslab, M, 384]."""
     _chk(slabs, F32, "slabs"); _chk(resid, F32, "resid"); _chk(z, F32, "z"); _chk(y, F32, "y")
-    L.call("sais_temporal_ln_fwd", _p(slabs), slabs.shape[0], slabs.stride(0), _p(bias), _p(resid), slabs.shape[1],
-           0.0 if drop is None else float(drop[0]), None if drop is None else _p(drop[1]), 0 if drop is None else int(drop[2]),
-           _p(y), _p(gamma), _p(beta), eps, _p(z), _p(mean), _p(rstd), _stream())
+    L.call("sais_temporal_ln_fwd", *_slabs3(slabs), _p(bias), _p(resid), slabs.shape[1], *_drop3(drop), _p(y), _p(gamma), _p(beta), eps, _p(z), _p(mean), _p(rstd), _stream())
 
 
 def temporal_ln_bwd(slabs, add, x, mean, rstd, gamma, dx, dx_drop=None, drop=None, dgamma=None, dbeta=None):
     """dy = sum_z slabs[z] + add ; dx = LayerNorm'(dy) at (x, mean, rstd) ; dx_drop = drop(dx)."""
     _chk(slabs, F32, "slabs"); _chk(add, F32, "add"); _chk(x, F32, "x"); _chk(dx, F32, "dx"); _chk(dx_drop, F32, "dx_drop")
     rows = x.shape[0]
-    L.call("sais_temporal_ln_bwd", _p(slabs), 0 if slabs is None else slabs.shape[0], 0 if slabs is None else slabs.stride(0),
-           _p(add), _p(x), _p(mean), _p(rstd), _p(gamma), rows, _p(dx), _p(dx_drop),
-           0.0 if drop is None else float(drop[0]), None if drop is None else _p(drop[1]), 0 if drop is None else int(drop[2]),
-           _p(dgamma), _p(dbeta), _stream())
+    L.call("sais_temporal_ln_bwd", *_slabs3(slabs), _p(add), _p(x), _p(mean), _p(rstd), _p(gamma), rows, _p(dx), _p(dx_drop),
+           *_drop3(drop), _p(dgamma), _p(dbeta), _stream())
 
 
 def gemm_tn(p, q, dW, db=None, nsplit=None):
@@ -280,11 +292,7 @@ def gemm_tn(p, q, dW, db=None, nsplit=None):
     _chk(p, F32 if f32 else BF16, "P"); _chk(q, F32 if f32 else BF16, "Q"); _chk(dW, F32, "dW"); _chk(db, F32, "db")
     M, N1 = p.shape
     N2 = q.shape[1]
-    if nsplit is None:
-        tiles = (N1 // 128) * (N2 // 128)
-        # measured sweep on MI355X (tools/gemm_bench.py): ~430 workgroups is the sweet spot between chip
-        # fill (2 workgroups/CU) and fp32-atomic traffic (64 KiB per workgroup)
-        nsplit = max(1, min((M + 255) // 256, (432 + tiles - 1) // tiles))
+    nsplit = _tn_nsplit(nsplit, M, (N1 // 128) * (N2 // 128))
     _timed("gemm_tn_f32" if f32 else "gemm_tn", 2.0 * M * N1 * N2, p.element_size() * M * (N1 + N2) + 4 * N1 * N2,
            lambda: L.call("sais_gemm_tn_f32" if f32 else "sais_gemm_tn", _p(p), p.stride(0), _p(q), q.stride(0), M, N1,
                           N2, _p(dW), dW.stride(0), _p(db), nsplit, _stream()))
@@ -298,13 +306,12 @@ def gemm_tn_grouped(items, M, nsplit=None):
     f32 = items[0][0].dtype == F32
     for i, (p, q, dW, db) in enumerate(items):
         _chk(p, F32 if f32 else BF16, "P"); _chk(q, F32 if f32 else BF16, "Q"); _chk(dW, F32, "dW"); _chk(db, F32, "db")
-        N1, N2 = p.shape[1], q.shape[1]
-        arr[i] = L.SaisTnItem(_p(p), p.stride(0), _p(q), q.stride(0), N1, N2, _p(dW), dW.stride(0), _p(db))
+        arr[i] = _tn_item(p, q, dW, db)
+        N1, N2 = arr[i].N1, arr[i].N2
         tiles += (N1 // 128) * (N2 // 128)
         flops += 2.0 * M * N1 * N2
         nbytes += 2 * M * (N1 + N2) + 4 * N1 * N2
-    if nsplit is None:
-        nsplit = max(1, min((M + 255) // 256, (432 + tiles - 1) // tiles))
+    nsplit = _tn_nsplit(nsplit, M, tiles)
     # one tag per distinct launch shape: the full four-GEMM dW of a block, the last block's qkv-only and compact launches and
     # the temporal layers' are different kernels in all but name, and a pooled average would describe none of them
     tag = ("gemm_tn_grouped_f32" if f32 else "gemm_tn_grouped") + ("" if f32 else f"[{len(items)} GEMMs,M{M}]")
@@ -350,8 +357,7 @@ def layernorm_bwd(x, ldx, mean, rstd, gamma, rows, dy16=None, dy32=None, dres=No
     _chk(dx32_drop, F32, "dx32_drop")
     L.call("sais_layernorm_bwd", _p(dy16), lddy16, _p(dy32), lddy32, _p(x), ldx, _p(mean), _p(rstd), _p(gamma),
            _p(dres), lddres, rows, 384, _p(dx32), lddx32, _p(dx16), lddx16, _p(dgamma), _p(dbeta), _p(rowscale16),
-           _p(dx32_drop), 0.0 if drop is None else float(drop[0]), None if drop is None else _p(drop[1]),
-           0 if drop is None else int(drop[2]), _stream())
+           _p(dx32_drop), *_drop3(drop), _stream())
 
 
 def vit_attn_fwd(qkv, frames, out, lse=None, probs=None, ntok=197):
@@ -445,9 +451,7 @@ def vit_blocks_dw(pending, extra=()):
     Ps = (ctypes.POINTER(L.SaisVitBlockParams) * n)(*[ctypes.pointer(P) for P, _, _ in pending])
     As = (ctypes.POINTER(L.SaisVitBlockBwd) * n)(*[ctypes.pointer(a) for _, a, _ in pending])
     Ws = (ctypes.c_void_p * n)(*[_p(ws) for _, _, ws in pending])
-    ex = (L.SaisTnItem * max(1, len(extra)))()
-    for i, (p, q, dW, db) in enumerate(extra):
-        ex[i] = L.SaisTnItem(_p(p), p.stride(0), _p(q), q.stride(0), p.shape[1], q.shape[1], _p(dW), dW.stride(0), _p(db))
+    ex = (L.SaisTnItem * max(1, len(extra)))(*[_tn_item(*item) for item in extra])
     L.call("sais_vit_blocks_dw", Ps, As, Ws, min(ws.numel() for _, _, ws in pending), n, ex, len(extra), _stream())
 
 
@@ -469,11 +473,12 @@ def temporal_layer_params(f, prefix):
     return P
 
 
-def temporal_layer_fwd(P, B, S, z, pad, qkv, ctx, attn, y1, z1, m1, r1, h, y2, zo, m2, r2, drop, site0, ws):
-    """One post-norm TransformerEncoderLayer forward as ONE C call (sais_temporal_layer_fwd).  drop = (p, rng) or None."""
-    pd, rng = drop if drop is not None else (0.0, None)
-    a = L.SaisTemporalLayerFwd(B, S, _p(z), _p(pad), _p(qkv), _p(ctx), _p(attn), _p(y1), _p(z1), _p(m1), _p(r1), _p(h), _p(y2),
-                               _p(zo), _p(m2), _p(r2), float(pd), _p(rng), int(site0))
+def temporal_layer_fwd(P, B, S, t, pad, attn, drop, site0, ws):
+    """One post-norm TransformerEncoderLayer forward as ONE C call (sais_temporal_layer_fwd); t = the layer's tensors (z in, zo
+    out).  drop = (p, rng) or None."""
+    a = L.SaisTemporalLayerFwd(B, S, _p(t["z"]), _p(pad), _p(t["qkv"]), _p(t["ctx"]), _p(attn), _p(t["y1"]), _p(t["z1"]),
+                               _p(t["m1"]), _p(t["r1"]), _p(t["h"]), _p(t["y2"]), _p(t["zo"]), _p(t["m2"]), _p(t["r2"]),
+                               *_drop3(drop, site0))
     L.call("sais_temporal_layer_fwd", ctypes.byref(P), ctypes.byref(a), _p(ws), ws.numel(), _stream())
 
 
@@ -482,15 +487,10 @@ def temporal_layer_bwd(P, B, S, a, pad, slabs, add, dx_slabs, dx_add, drop, site
     the layer output comes as raw slabs + add and the gradient of its input leaves the same way (dx_slabs, dx_add).
     dw_items = (SaisTnItem array, first index): the layer's four weight-gradient GEMMs are written there instead of being
     launched (temporal_dw_deferred launches them; `ws` must stay untouched until then)."""
-    pd, rng = drop if drop is not None else (0.0, None)
-    items_ptr = None
-    if dw_items is not None:
-        arr, first = dw_items
-        items_ptr = ctypes.addressof(arr) + first * ctypes.sizeof(L.SaisTnItem)
+    items_ptr = None if dw_items is None else ctypes.addressof(dw_items[0]) + dw_items[1] * ctypes.sizeof(L.SaisTnItem)
     g = L.SaisTemporalLayerBwd(B, S, _p(a["z"]), _p(a["qkv"]), _p(a["ctx"]), _p(a["y1"]), _p(a["m1"]), _p(a["r1"]), _p(a["z1"]),
-                               _p(a["h"]), _p(a["y2"]), _p(a["m2"]), _p(a["r2"]), _p(pad), _p(slabs),
-                               0 if slabs is None else slabs.shape[0], 0 if slabs is None else slabs.stride(0), _p(add),
-                               _p(dx_slabs), _p(dx_add), float(pd), _p(rng), int(site0), items_ptr)
+                               _p(a["h"]), _p(a["y2"]), _p(a["m2"]), _p(a["r2"]), _p(pad), *_slabs3(slabs), _p(add),
+                               _p(dx_slabs), _p(dx_add), *_drop3(drop, site0), items_ptr)
     L.call("sais_temporal_layer_bwd", ctypes.byref(P), ctypes.byref(g), _p(ws), ws.numel(), _stream())
 
 
@@ -663,8 +663,7 @@ def temporal_prepare_fwd(x, clip_stride, frame_stride, pos, cls, B, T, z32, z16)
 def temporal_prepare_bwd(dz32, slabs, B, T, dx, clip_stride, frame_stride, accumulate, dpos, dcls):
     """dz = dz32 (f32 [B*(T+1),384] or None) + sum of the raw split-K slabs (f32 [nslab, B*(T+1), 384] or None)."""
     _chk(dz32, F32, "dz32"); _chk(slabs, F32, "slabs")
-    L.call("sais_temporal_prepare_bwd", _p(dz32), _p(slabs), 0 if slabs is None else slabs.shape[0],
-           0 if slabs is None else slabs.stride(0), B, T, _p(dx), clip_stride, frame_stride,
+    L.call("sais_temporal_prepare_bwd", _p(dz32), *_slabs3(slabs), B, T, _p(dx), clip_stride, frame_stride,
            1 if accumulate else 0, _p(dpos), _p(dcls), _stream())
 
 

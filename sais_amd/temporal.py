@@ -22,14 +22,15 @@ training raises inside the reference), multi-domain models ('+' in the domain) s
 (clip, snippet) pair is one sequence of the encoder, the head averages the ReLU'd CLS rows over the snippets of a clip
 (:381-382) and the returned attention map is [B*nsnippets, T+1, T+1], as in the reference.
 """
+import os as _os
+from types import SimpleNamespace
+
 import torch
 import torch.nn as nn
 
 from . import _lib as L
 from . import ops
-from .flat import FlatParams
-
-import os as _os
+from .flat import ensure_flat
 
 _LAYER_CALLS = _os.environ.get('SAIS_TEMPORAL_LAYER_CALLS', '1') != '0'      # one C call per encoder layer and direction
 _PREFETCH = _os.environ.get('SAIS_TEMPORAL_PREFETCH', '0') == '1'        # measured: no net gain (LABNOTES R4.3): off
@@ -105,7 +106,6 @@ class fullModel(nn.Module):
         self.modalities, self.self_attention, self.importance_loss = modalities, self_attention, importance_loss
         self.data_type, self.encoder_type = data_type, encoder_type
         self.flat = None
-        self._sig = None
         self._anchor = None
         self.grad_ready_hook = None
         self._wsbuf = {}               # scratch of the layer-level calls (ops.cached_workspace)
@@ -127,12 +127,8 @@ class fullModel(nn.Module):
         return f"{enc}.layers.{l}."
 
     def _t_names(self):
-        out = []
-        for l in range(self.nlayers):
-            p = self._lnames(l)
-            out += [p + "self_attn.in_proj_weight", p + "self_attn.out_proj.weight", p + "linear1.weight",
-                    p + "linear2.weight"]
-        return out
+        return [self._lnames(l) + n for l in range(self.nlayers)
+                for n in ("self_attn.in_proj_weight", "self_attn.out_proj.weight", "linear1.weight", "linear2.weight")]
 
     def _mil_forward(self, x, f, xpad, fpad):
         """task 'MIL' (prepare_model.py:356-361), inference: per-snippet frame encoder -> relu'd CLS rows + clip position
@@ -155,14 +151,15 @@ class fullModel(nn.Module):
         fl = self._engine(dev)
         B, ns = x.shape[0], x.shape[1]
         S = x.shape[2] + 1
+        pl = self._plan()
         with torch.no_grad():
-            zr, _, _ = self._stream_fwd(x, xpad, save=False, want_attn=False)
+            zr, _, _ = self._stream_fwd(x, xpad, pl, save=False, want_attn=False)
             tokens = torch.empty(B * ns, D, dtype=torch.float32, device=dev)
             o = fl.offsets["clip_pos_embeddings.0"]
             assert fl.offsets[f"clip_pos_embeddings.{ns - 1}"] == o + (ns - 1) * D
             ops.mil_forward(zr, S * D, fl.flat[o:o + ns * D], B, ns, tokens)
             nopad = torch.zeros(B, ns, dtype=torch.uint8, device=dev)
-            enc, _, _ = self._encoder_fwd(tokens, nopad, B, ns, "transEncoderClip", save=False, want_attn=False)
+            enc, _, _ = self._encoder_fwd(tokens, nopad, B, ns, "transEncoderClip", pl, save=False, want_attn=False)
             reps = torch.empty(B, ns, D, dtype=torch.float32, device=dev)
             logits = torch.empty(B, self.nclasses, dtype=torch.float32, device=dev)
             att = torch.empty(self.nclasses, B, ns, dtype=torch.float32, device=dev)
@@ -173,29 +170,39 @@ class fullModel(nn.Module):
                          cat("finalModules.%d.bias").reshape(-1), reps, logits, att)
         return tokens.view(B, ns, D).permute(1, 0, 2), reps, logits, {c: att[c] for c in range(self.nclasses)}
 
-    def _sentinels(self):
-        return ["linear.weight", "frame_cls", "frame_pos_embeddings.0", self._lnames(0) + "self_attn.in_proj_weight",
-                self._lnames(self.nlayers - 1) + "linear2.weight"]
-
     def _engine(self, device):
-        if self.flat is None or not self.flat.intact() or self.flat.device != device:
-            self.flat = FlatParams(self, device, f32_transposes=True)
+        sentinels = ("linear.weight", "frame_cls", "frame_pos_embeddings.0", self._lnames(0) + "self_attn.in_proj_weight",
+                     self._lnames(self.nlayers - 1) + "linear2.weight")
+        if ensure_flat(self, device, f32_transposes=True, transposed=self._t_names(), sentinels=sentinels):
             self._anchor = torch.zeros(1, device=device, requires_grad=True)
-            self._sig = None
-        sig = self.flat.signature(self._sentinels())
-        if sig != self._sig:
-            self.flat.refresh_shadows(self._t_names())
-            self._sig = self.flat.signature(self._sentinels())
+        self.flat.fresh()
         return self.flat
 
     def load_state_dict(self, *a, **k):
-        r = super().load_state_dict(*a, **k)
-        self._sig = None
-        return r
+        if self.flat is not None:
+            self.flat.mark_dirty()
+        return super().load_state_dict(*a, **k)
 
     def sgd_step(self, lr, grad_scale=1.0):
-        self.flat.sgd_step(lr, grad_scale, self._t_names())
-        self._sig = self.flat.signature(self._sentinels())
+        self.flat.sgd_step(lr, grad_scale)
+
+    # ------------------------------------------------------------------ dropout
+    def _site(self, sidx, l):              # first of the four sites (attention weights, dropout1, dropout, dropout2) of a layer
+        return (sidx * self.nlayers + l) * 4
+
+    @staticmethod
+    def _drop3(drop, site):                # drop = (p, rng state) | None -> the (p, rng, site) triple the fused consumers take
+        return None if drop is None else (drop[0], drop[1], site)
+
+    def _draw_dropout(self, dev):
+        """train() with dropout_p > 0: advance the Philox state and return drop = (p, state of this pass); else None."""
+        if not (self.training and self.dropout_p > 0):
+            return None
+        if self._rng is None or self._rng.device != dev:
+            self._rng = ops.rng_state(self.dropout_seed, dev)
+        ops.rng_advance(self._rng)                        # a graph node: every replay draws fresh masks
+        self.last_dropout_state = self._rng.clone()       # what this forward and its backward regenerate the masks from
+        return float(self.dropout_p), self.last_dropout_state
 
     def dropout_masks(self, state, Bn, S, stream=0):
         """The keep masks a train-mode forward with RNG state `state` (= self.last_dropout_state) applied to stream 0 (RGB) /
@@ -203,10 +210,29 @@ class fullModel(nn.Module):
         bool.  For tests: the oracle applies the same masks."""
         out, p, dev = [], float(self.dropout_p), state.device
         for l in range(self.nlayers):
-            site = (stream * self.nlayers + l) * 4
+            site = self._site(stream, l)
             m = lambda k, *sh: ops.dropout_mask(int(torch.tensor(sh).prod()), p, state, site + k, dev).view(*sh).bool()
             out.append(dict(attn=m(0, Bn, TH, S, S), d1=m(1, Bn, S, D), ff=m(2, Bn, S, FF), d2=m(3, Bn, S, D)))
         return out
+
+    # ------------------------------------------------------------------ decisions
+    def _streams(self):
+        return self.modalities in ('RGB', 'RGB-Flow'), self.modalities in ('Flow', 'RGB-Flow')
+
+    def _plan(self, drop=None):
+        """Every decision of a pass, taken once at its top (the module switches are read here, at call time: tests assign them)."""
+        use_x, use_f = self._streams()
+        layer_calls = _LAYER_CALLS and ops.TIMER is None          # one C call per layer and direction; a timer wants the launches
+        return SimpleNamespace(layer_calls=layer_calls, dw_defer=layer_calls and _DW_DEFER, use_x=use_x, use_f=use_f, drop=drop)
+
+    def _wants_autograd(self):
+        return torch.is_grad_enabled() and self.linear.weight.requires_grad
+
+    def merged_pass_ok(self, stacked=False):
+        """May the TTA versions of a call go through ONE encoder pass (`_tta_core`)?  stacked: the caller stacks both streams
+        itself and has no per-sample domains (inference.run_windows), which fits a single-domain two-stream model."""
+        ok = _TTA_MERGE and not self.importance_loss and not self._wants_autograd()
+        return ok and (not stacked or (self.modalities == 'RGB-Flow' and '+' not in self.domain))
 
     # ------------------------------------------------------------------ reference signature
     def forward(self, x, f, xlens, flens, task, xpad, fpad, domains=None):
@@ -226,7 +252,7 @@ class fullModel(nn.Module):
             second = torch.tensor([0 if d == 'NH_02' else 1 for d in domains], dtype=torch.uint8, device=dev)
         if isinstance(x, (list, tuple)) or isinstance(f, (list, tuple)):          # TTA versions, :331-346
             n = len(x) if x is not None else len(f)
-            if _TTA_MERGE and not self.importance_loss and not (torch.is_grad_enabled() and self.linear.weight.requires_grad):
+            if self.merged_pass_ok():
                 return self._forward_tta_merged(x, f, xpad, fpad, second, n)
             embs, attn0, imp0 = [], None, None
             for v in range(n):
@@ -246,8 +272,7 @@ class fullModel(nn.Module):
         batch; 20 % of a long video's inference time, LABNOTES R5.3) are stacked along the sequence axis, padded to the longest
         version under the key-padding mask, and run once.  Same values as the per-version passes up to the summation order of
         the masked softmax (tests: test_temporal_tta_list_path, test_tta_merged_pass_equals_per_version_passes)."""
-        use_x = self.modalities in ('RGB', 'RGB-Flow')
-        use_f = self.modalities in ('Flow', 'RGB-Flow')
+        use_x, use_f = self._streams()
         parts = []                                               # (stream, version, [B, ns, T, 384], mask [B * ns, T + 1])
         for name, on, ts, pads in (("x", use_x, xs, xpads), ("f", use_f, fs, fpads)):
             if not on:
@@ -275,43 +300,29 @@ class fullModel(nn.Module):
     def _tta_core(self, X, P, where, B, ns, n, second=None):
         """X f32 [tot, 1, Tm, 384] stacked sequences (zero padded), P u8 [tot, Tm + 1] key-padding masks, where[(stream, version)] =
         (first sequence, count, T): one encoder pass, then the head per version.  Returns (embs, version 0's attention map)."""
-        use_x = self.modalities in ('RGB', 'RGB-Flow')
-        use_f = self.modalities in ('Flow', 'RGB-Flow')
-        dev = X.device
-        fl = self._engine(dev)
+        pl = self._plan()                                        # no dropout: an inference pass, whatever the mode
+        self._engine(X.device)
         tot, S = X.shape[0], X.shape[2] + 1
-        z, attn, _ = self._stream_fwd(X, P, save=False, want_attn=True)
+        z, attn, _ = self._stream_fwd(X, P, pl, save=False, want_attn=True)
         z = z.view(tot, S * D)
-        embs = []
-        for v in range(n):
-            zr = z[where[("x", v)][0]:where[("x", v)][0] + B * ns] if use_x else None
-            zf = z[where[("f", v)][0]:where[("f", v)][0] + B * ns] if use_f else None
-            if use_x and use_f and where[("x", v)][1] != where[("f", v)][1]:
-                raise ValueError("RGB and flow streams must have the same batch size and number of snippets")
-            rep = torch.empty(B, D, dtype=torch.float32, device=dev)
-            emb = torch.empty(B, EMB, dtype=torch.float32, device=dev)
-            ops.head_fwd(zr, zf, S * D, B, fl.w32("linear.weight"), fl.w32("linear.bias"), rep, emb, clip_stride_flow=S * D,
-                         nsnippets=ns, second=None if second is None else (second, fl.w32("linearB.weight"), fl.w32("linearB.bias")))
-            embs.append(emb)
+        seqs = lambda on, key: z[where[key][0]:where[key][0] + where[key][1]].view(-1, ns, S * D) if on else None
+        embs = [self._head_fwd(seqs(pl.use_x, ("x", v)), seqs(pl.use_f, ("f", v)), second)[1] for v in range(n)]
         # the returned map is version 0's, of the RGB stream when there is one (:436-443): its own [T0 + 1, T0 + 1] corner
-        o0, k0, T0 = where[("x", 0) if use_x else ("f", 0)]
-        attn0 = attn[o0:o0 + k0, :T0 + 1, :T0 + 1].contiguous()
-        return embs, attn0
+        o0, k0, T0 = where[("x", 0) if pl.use_x else ("f", 0)]
+        return embs, attn[o0:o0 + k0, :T0 + 1, :T0 + 1].contiguous()
 
     def _forward_one(self, x, f, xpad, fpad, second=None):
-        use_x = self.modalities in ('RGB', 'RGB-Flow')
-        use_f = self.modalities in ('Flow', 'RGB-Flow')
+        use_x, use_f = self._streams()
         x = self._check(x, "x") if use_x else None
         f = self._check(f, "f") if use_f else None
         dev = (x if x is not None else f).device
         xpad = self._mask(xpad, x, dev) if use_x else None
         fpad = self._mask(fpad, f, dev) if use_f else None
         self._engine(dev)
-        if torch.is_grad_enabled() and self.linear.weight.requires_grad:
+        if self._wants_autograd():
             emb, attn, imp = _TemporalFn.apply(self, x, f, xpad, fpad, self._anchor, second)
             return emb, attn, (imp if self.importance_loss else None)
-        emb, attn, imp, _ = self._forward_kernels(x, f, xpad, fpad, save=False, second=second)
-        return emb, attn, imp
+        return self._forward_kernels(x, f, xpad, fpad, save=False, second=second)[:3]
 
     @staticmethod
     def _check(t, name):
@@ -344,9 +355,8 @@ class fullModel(nn.Module):
         out = torch.empty(ns, M, N, dtype=torch.float32, device=a.device)
         return ops.tgemm(a, w, L.TG_RAW, out, nsplit=ns)
 
-    def _stream_fwd(self, x, pad, save, want_attn, drop=None, sidx=0):
-        fl = self.flat
-        dev = x.device
+    def _stream_fwd(self, x, pad, pl, save, want_attn, sidx=0):
+        fl, dev = self.flat, x.device
         x = x.reshape(x.shape[0] * x.shape[1], 1, x.shape[2], D)       # (clip, snippet) pairs are independent sequences
         B, _, T, _ = x.shape
         S, M = T + 1, B * (T + 1)
@@ -356,59 +366,53 @@ class fullModel(nn.Module):
         o = fl.offsets["frame_pos_embeddings.0"]
         assert fl.offsets[f"frame_pos_embeddings.{T - 1}"] == o + (T - 1) * D      # rows contiguous in the flat buffer
         ops.temporal_prepare_fwd(x, x.stride(0), x.stride(2), fl.flat[o:o + T * D], fl.w32("frame_cls"), B, T, z, None)
-        z, attn, layers = self._encoder_fwd(z, pad, B, S, "transEncoderFrame", save, want_attn, drop, sidx)
-        return z, attn, dict(layers=layers, pad=pad, B=B, T=T, x=x, drop=drop, sidx=sidx) if save else None
+        z, attn, layers = self._encoder_fwd(z, pad, B, S, "transEncoderFrame", pl, save, want_attn, sidx)
+        return z, attn, dict(layers=layers, pad=pad, B=B, T=T, x=x, drop=pl.drop, sidx=sidx) if save else None
 
-    def _encoder_fwd(self, z, pad, B, S, enc, save, want_attn, drop=None, sidx=0):
+    @staticmethod
+    def _layer_buffers(M, save, dev):
+        """The tensors one layer writes, for whichever form issues it; y / mean / rstd of the two LayerNorms only with `save`."""
+        e32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        t = dict(qkv=e32(M, 3 * D), ctx=e32(M, D), z1=e32(M, D), h=e32(M, FF), zo=e32(M, D))
+        t.update({k: e32(M, D) if save else None for k in ("y1", "y2")})
+        t.update({k: e32(M) if save else None for k in ("m1", "r1", "m2", "r2")})
+        return t
+
+    def _encoder_fwd(self, z, pad, B, S, enc, pl, save, want_attn, sidx=0):
         """The four post-norm layers of `enc` (transEncoderFrame | transEncoderClip) over B sequences of S tokens,
         z f32 [B*S, 384]; pad u8 [B, S] (1 = masked key).  Returns (output, last layer's head-averaged attention, saved)."""
-        fl = self.flat
-        dev = z.device
-        M = B * S
-        e32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-        layers = []
-        attn = None
+        dev, layers = z.device, []
+        attn = torch.empty(B, S, S, dtype=torch.float32, device=dev) if want_attn else None
         for l in range(self.nlayers):
             p = self._lnames(l, enc)
-            last = l == self.nlayers - 1
-            qkv, ctx = e32(M, 3 * D), e32(M, D)
-            if want_attn and last:
-                attn = e32(B, S, S)
-            if _LAYER_CALLS and ops.TIMER is None:       # one C call per layer (sais_temporal_layer_fwd: the launches below)
-                y1, y2 = (e32(M, D), e32(M, D)) if save else (None, None)
-                z1, zo, h = e32(M, D), e32(M, D), e32(M, FF)
-                m1, r1, m2, r2 = (e32(M), e32(M), e32(M), e32(M)) if save else (None, None, None, None)
-                ops.temporal_layer_fwd(self._layer_params(p), B, S, z, pad, qkv, ctx, attn if last else None, y1, z1, m1, r1, h,
-                                       y2, zo, m2, r2, drop, (sidx * self.nlayers + l) * 4,
+            t = dict(self._layer_buffers(B * S, save, dev), z=z)
+            amap = attn if l == self.nlayers - 1 else None
+            if pl.layer_calls:                                   # sais_temporal_layer_fwd: the launches of _layer_fwd_launches
+                ops.temporal_layer_fwd(self._layer_params(p), B, S, t, pad, amap, pl.drop, self._site(sidx, l),
                                        ops.cached_workspace(self._wsbuf, L.OP_TEMPORAL_LAYER_FWD, B, S, dev))
-                if save:
-                    layers.append(dict(z=z, qkv=qkv, ctx=ctx, y1=y1, m1=m1, r1=r1, z1=z1, h=h, y2=y2, m2=m2, r2=r2))
-                z = zo
-                continue
-            ops.tgemm(z, fl.w32(p + "self_attn.in_proj_weight"), L.TG_BIAS, qkv, bias=fl.w32(p + "self_attn.in_proj_bias"))
-            # train mode: dropout sites 0-3 of this layer (attention weights, dropout1, dropout, dropout2)
-            site = (sidx * self.nlayers + l) * 4
-            pd, rng = drop if drop is not None else (0.0, None)
-            ops.temporal_attn_fwd(qkv, pad, B, S, ctx, attn if last else None, p_drop=pd, rng=rng, site=site)
-            dsite = (lambda k: None if drop is None else (pd, rng, site + k))      # dropout fused into the consumers
-            # src = norm1(src + dropout1(out_proj(ctx)))
-            y1 = e32(M, D) if save else None
-            z1, m1, r1 = e32(M, D), (e32(M) if save else None), (e32(M) if save else None)
-            ops.temporal_ln_fwd(self._raw(ctx, fl.w32(p + "self_attn.out_proj.weight")), fl.w32(p + "self_attn.out_proj.bias"),
-                                z, fl.w32(p + "norm1.weight"), fl.w32(p + "norm1.bias"), 1e-5, z1, y=y1, mean=m1, rstd=r1,
-                                drop=dsite(1))
-            # src = norm2(src + dropout2(linear2(dropout(relu(linear1(src))))))
-            h = e32(M, FF)
-            ops.tgemm(z1, fl.w32(p + "linear1.weight"), L.TG_BIAS_RELU, h, bias=fl.w32(p + "linear1.bias"), drop=dsite(2))
-            y2 = e32(M, D) if save else None
-            zo, m2, r2 = e32(M, D), (e32(M) if save else None), (e32(M) if save else None)
-            ops.temporal_ln_fwd(self._raw(h, fl.w32(p + "linear2.weight")), fl.w32(p + "linear2.bias"), z1,
-                                fl.w32(p + "norm2.weight"), fl.w32(p + "norm2.bias"), 1e-5, zo, y=y2, mean=m2, rstd=r2,
-                                drop=dsite(3))
+            else:
+                self._layer_fwd_launches(p, B, S, t, pad, amap, pl.drop, self._site(sidx, l))
             if save:
-                layers.append(dict(z=z, qkv=qkv, ctx=ctx, y1=y1, m1=m1, r1=r1, z1=z1, h=h, y2=y2, m2=m2, r2=r2))
-            z = zo
+                layers.append(t)
+            z = t["zo"]
         return z, attn, layers
+
+    def _layer_fwd_launches(self, p, B, S, t, pad, amap, drop, site):
+        fl = self.flat
+        ops.tgemm(t["z"], fl.w32(p + "self_attn.in_proj_weight"), L.TG_BIAS, t["qkv"], bias=fl.w32(p + "self_attn.in_proj_bias"))
+        # train mode: dropout sites 0-3 of this layer (attention weights, dropout1, dropout, dropout2), fused into the consumers
+        pd, rng = drop if drop is not None else (0.0, None)
+        ops.temporal_attn_fwd(t["qkv"], pad, B, S, t["ctx"], amap, p_drop=pd, rng=rng, site=site)
+        # src = norm1(src + dropout1(out_proj(ctx)))
+        ops.temporal_ln_fwd(self._raw(t["ctx"], fl.w32(p + "self_attn.out_proj.weight")), fl.w32(p + "self_attn.out_proj.bias"),
+                            t["z"], fl.w32(p + "norm1.weight"), fl.w32(p + "norm1.bias"), 1e-5, t["z1"], y=t["y1"], mean=t["m1"],
+                            rstd=t["r1"], drop=self._drop3(drop, site + 1))
+        # src = norm2(src + dropout2(linear2(dropout(relu(linear1(src))))))
+        ops.tgemm(t["z1"], fl.w32(p + "linear1.weight"), L.TG_BIAS_RELU, t["h"], bias=fl.w32(p + "linear1.bias"),
+                  drop=self._drop3(drop, site + 2))
+        ops.temporal_ln_fwd(self._raw(t["h"], fl.w32(p + "linear2.weight")), fl.w32(p + "linear2.bias"), t["z1"],
+                            fl.w32(p + "norm2.weight"), fl.w32(p + "norm2.bias"), 1e-5, t["zo"], y=t["y2"], mean=t["m2"],
+                            rstd=t["r2"], drop=self._drop3(drop, site + 3))
 
     def _layer_params(self, prefix):
         """ctypes parameter block of one encoder layer (pointers into the flat buffers), rebuilt when those are."""
@@ -437,36 +441,35 @@ class fullModel(nn.Module):
             hi = fl.offsets["transEncoderClip.layers.0.self_attn.in_proj_weight"]
             ops.touch(fl.flat[lo:hi])
 
+    def _head_fwd(self, zr, zf, second):
+        """The fused head over the encoder outputs of the streams that run, each f32 [B, nsnippets, S * 384] (the two may differ
+        in S: inference has 15 RGB frames and 1-2 flow frames per window).  Returns (rep [B, 384], emb [B, 256])."""
+        if zr is not None and zf is not None and zr.shape[:2] != zf.shape[:2]:
+            raise ValueError("RGB and flow streams must have the same batch size and number of snippets")
+        fl, ref = self.flat, zr if zr is not None else zf
+        B, ns = ref.shape[:2]
+        rep, emb = (torch.empty(B, n, dtype=torch.float32, device=ref.device) for n in (D, EMB))
+        ops.head_fwd(zr, zf, ref.shape[2], B, fl.w32("linear.weight"), fl.w32("linear.bias"), rep, emb,
+                     clip_stride_flow=(zf if zf is not None else ref).shape[2], nsnippets=ns,
+                     second=None if second is None else (second, fl.w32("linearB.weight"), fl.w32("linearB.bias")))
+        return rep, emb
+
     def _forward_kernels(self, x, f, xpad, fpad, save, second=None):
         fl = self.flat
+        ref = x if x is not None else f
         self._prefetch(False)
+        pl = self._plan(self._draw_dropout(ref.device))
         zr = zf = sr = sf = attn = None
-        drop = None
-        if self.training and self.dropout_p > 0:
-            dev = (x if x is not None else f).device
-            if self._rng is None or self._rng.device != dev:
-                self._rng = ops.rng_state(self.dropout_seed, dev)
-            ops.rng_advance(self._rng)                        # a graph node: every replay draws fresh masks
-            self.last_dropout_state = self._rng.clone()       # what this forward and its backward regenerate the masks from
-            drop = (float(self.dropout_p), self.last_dropout_state)
         if x is not None:
-            zr, attn, sr = self._stream_fwd(x, xpad, save, want_attn=True, drop=drop, sidx=0)
+            zr, attn, sr = self._stream_fwd(x, xpad, pl, save, want_attn=True, sidx=0)
         if f is not None:
-            zf, fattn, sf = self._stream_fwd(f, fpad, save, want_attn=(x is None), drop=drop, sidx=1)
+            zf, fattn, sf = self._stream_fwd(f, fpad, pl, save, want_attn=(x is None), sidx=1)
             if x is None:
                 attn = fattn
-        ref = x if x is not None else f
-        B, ns = ref.shape[0], ref.shape[1]
-        # the two streams may have different lengths (inference: 15 RGB frames vs 1-2 flow frames per window)
-        Sx = x.shape[2] + 1 if x is not None else f.shape[2] + 1
+        (B, ns), Sx = ref.shape[:2], ref.shape[2] + 1
         Sf = f.shape[2] + 1 if f is not None else Sx
-        if x is not None and f is not None and tuple(x.shape[:2]) != tuple(f.shape[:2]):
-            raise ValueError("RGB and flow streams must have the same batch size and number of snippets")
-        rep = torch.empty(B, D, dtype=torch.float32, device=ref.device)
-        emb = torch.empty(B, EMB, dtype=torch.float32, device=ref.device)
-        ops.head_fwd(zr, zf, (Sx if zr is not None else Sf) * D, B, fl.w32("linear.weight"), fl.w32("linear.bias"), rep, emb,
-                     clip_stride_flow=Sf * D, nsnippets=ns,
-                     second=None if second is None else (second, fl.w32("linearB.weight"), fl.w32("linearB.bias")))
+        rep, emb = self._head_fwd(None if x is None else zr.view(*x.shape[:2], Sx * D),
+                                  None if f is None else zf.view(*f.shape[:2], Sf * D), second)
         imp = None
         if self.importance_loss:                              # importance_function(full RGB sequence), :419-421
             imp = torch.empty(B, ns, Sx, 1, dtype=torch.float32, device=ref.device)
@@ -475,28 +478,21 @@ class fullModel(nn.Module):
                      xshape=None if x is None else x.shape, fshape=None if f is None else f.shape) if save else None
         return emb, attn, imp, saved
 
-    def _stream_bwd(self, s, dz, need_dx):
+    def _stream_bwd(self, s, dz, need_dx, pl):
         """dz: f32 [M,384] gradient wrt the stream's final (pre-ReLU) encoder output."""
         fl = self.flat
         dev = dz.device
-        B, T = s["B"], s["T"]
+        B, T, drop = s["B"], s["T"], s["drop"]
         S, M = T + 1, B * (T + 1)
         e32 = lambda *sh: torch.empty(*sh, dtype=torch.float32, device=dev)
         slabs, add = None, dz                      # the gradient entering a layer = sum of `slabs` (raw dX GEMM output) + add
-        layer_calls = _LAYER_CALLS and ops.TIMER is None
-        dw_items = ops.tn_items(4 * self.nlayers) if layer_calls and _DW_DEFER else None
+        dw_items = ops.tn_items(4 * self.nlayers) if pl.dw_defer else None
         keep = []                                  # per-layer gradients the deferred launch still reads
         for l in reversed(range(self.nlayers)):
             p = self._lnames(l)
             a = s["layers"][l]
-            # dropout backward = the same mask on the branch gradient (the residual path keeps the un-dropped one), fused:
-            # the LayerNorm backward emits dropout(dx) as a second output, and the drelu epilogue applies the FFN mask
-            # (a["h"] is the DROPPED relu output, so dropped units are already zero there: the mask rescales the kept ones)
-            drop = s.get("drop")
-            site = (s.get("sidx", 0) * self.nlayers + l) * 4
-            pd, rng = drop if drop is not None else (0.0, None)
-            dsite = (lambda k: None if drop is None else (pd, rng, site + k))
-            if layer_calls:                              # one C call per layer (sais_temporal_layer_bwd)
+            site = self._site(s["sidx"], l)
+            if pl.layer_calls:                           # one C call per layer (sais_temporal_layer_bwd)
                 ns = L.load().sais_tgemm_nsplit(M, D, 3 * D)
                 dx_slabs, dy1 = e32(ns, M, D), e32(M, D)
                 ws = ops.cached_workspace(self._wsbuf, L.OP_TEMPORAL_LAYER_BWD, B, S, dev, slot=l)
@@ -505,18 +501,22 @@ class fullModel(nn.Module):
                 keep += [ws, dy1]
                 slabs, add = dx_slabs, dy1
                 continue
+            # dropout backward = the same mask on the branch gradient (the residual path keeps the un-dropped one), fused:
+            # the LayerNorm backward emits dropout(dx) as a second output, and the drelu epilogue applies the FFN mask
+            # (a["h"] is the DROPPED relu output, so dropped units are already zero there: the mask rescales the kept ones)
+            pd, rng = drop if drop is not None else (0.0, None)
             dy2 = e32(M, D)
             dt2 = dy2 if drop is None else e32(M, D)
             ops.temporal_ln_bwd(slabs, add, a["y2"], a["m2"], a["r2"], fl.w32(p + "norm2.weight"), dy2,
-                                dx_drop=None if drop is None else dt2, drop=dsite(3),
+                                dx_drop=None if drop is None else dt2, drop=self._drop3(drop, site + 3),
                                 dgamma=fl.g(p + "norm2.weight"), dbeta=fl.g(p + "norm2.bias"))
             dh = e32(M, FF)
-            ops.tgemm(dt2, fl.wt16[p + "linear2.weight"], L.TG_DRELU, dh, aux=a["h"], drop=dsite(2))
+            ops.tgemm(dt2, fl.wt16[p + "linear2.weight"], L.TG_DRELU, dh, aux=a["h"], drop=self._drop3(drop, site + 2))
             dy1 = e32(M, D)                                   # LayerNorm'(dy2 (residual) + dh . W1)
             dt1 = dy1 if drop is None else e32(M, D)
             ops.temporal_ln_bwd(self._raw(dh, fl.wt16[p + "linear1.weight"]), dy2, a["y1"], a["m1"], a["r1"],
-                                fl.w32(p + "norm1.weight"), dy1, dx_drop=None if drop is None else dt1, drop=dsite(1),
-                                dgamma=fl.g(p + "norm1.weight"), dbeta=fl.g(p + "norm1.bias"))
+                                fl.w32(p + "norm1.weight"), dy1, dx_drop=None if drop is None else dt1,
+                                drop=self._drop3(drop, site + 1), dgamma=fl.g(p + "norm1.weight"), dbeta=fl.g(p + "norm1.bias"))
             dqkv = e32(M, 3 * D)
             ops.temporal_attn_bwd(a["qkv"], s["pad"], B, S, self._raw(dt1, fl.wt16[p + "self_attn.out_proj.weight"]), dqkv,
                                   p_drop=pd, rng=rng, site=site)
@@ -542,6 +542,7 @@ class fullModel(nn.Module):
 
     def _backward_kernels(self, saved, demb, needs, dimp=None):
         fl = self.flat
+        pl = self._plan()                          # the backward decides from its own inputs: the switches as they stand now
         fl.attach_grads()
         self._prefetch(True)
         B, ns, Sx, Sf = saved["B"], saved["ns"], saved["Sx"], saved["Sf"]
@@ -556,12 +557,8 @@ class fullModel(nn.Module):
         if dimp is not None:
             ops.importance_bwd(dimp, zr, fl.w32("importance_function.weight"), B * ns * Sx, dzr,
                                fl.g("importance_function.weight"), fl.g("importance_function.bias"))
-        dx = self._stream_bwd(saved["sr"], dzr, needs[0]) if zr is not None else None
-        df = self._stream_bwd(saved["sf"], dzf, needs[1]) if zf is not None else None
+        dx = self._stream_bwd(saved["sr"], dzr, needs[0], pl) if zr is not None else None
+        df = self._stream_bwd(saved["sf"], dzf, needs[1], pl) if zf is not None else None
         if self.grad_ready_hook:
             self.grad_ready_hook(0, fl.numel)
-        if dx is not None:
-            dx = dx.view(saved["xshape"])
-        if df is not None:
-            df = df.view(saved["fshape"])
-        return dx, df
+        return (None if dx is None else dx.view(saved["xshape"])), (None if df is None else df.view(saved["fshape"]))

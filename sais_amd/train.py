@@ -278,7 +278,7 @@ def trainModel(rank, world_size, root_path, savepath, dataset_name, data_type, b
         # one process): replicas must start from rank 0's, or the averaged gradients are applied to different parameters
         with torch.no_grad():
             sync.broadcast_initial_state([tm.flat.flat] + [p.data for p in model["prototypes"].values()])
-        tm._sig = None                                        # the bf16 / transposed shadows follow at the next forward
+        tm.flat.mark_dirty()                                  # the bf16 / transposed shadows follow at the next forward
         # longest window of any rank's shard: the position rows 0 .. T-1 are the only ones that receive gradients
         tmax = max((_longest_window(dataloader[ph].dataset) for ph in phases if ph in ("train", "train+val")), default=0)
         tmax = sync.agree_max(tmax, device)

@@ -28,7 +28,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops
-from .flat import FlatParams
+from .flat import ensure_flat
 
 D, NTOK, HEADS, HID, PATCH_K = 384, 197, 6, 1536, 768
 _PRUNE_Q = os.environ.get("SAIS_VIT_PRUNE_Q", "1") != "0"     # the CLS-only last block computes q for the CLS rows only
@@ -194,41 +194,28 @@ class VisionTransformer(nn.Module):
                 nn.init.constant_(m.bias, 0)
                 nn.init.constant_(m.weight, 1.0)
         self.flat = None
-        self._sig = None
         self._anchor = None
         self._interp = {}                            # frame side -> device f32 [ntok - 1, 196] bicubic map
         self.grad_ready_hook = None                  # callable(lo, hi): flat-grad slice [lo,hi) is final
-        self._t_names = []
-        for i in range(depth):
-            p = f"blocks.{i}."
-            self._t_names += [p + "attn.qkv.weight", p + "attn.proj.weight", p + "mlp.fc1.weight", p + "mlp.fc2.weight"]
-        self._sentinels = ["cls_token", "patch_embed.proj.weight", "blocks.0.attn.qkv.weight", "norm.weight",
-                           f"blocks.{depth - 1}.mlp.fc2.weight"]
+        self._t_names = [f"blocks.{i}.{n}.weight" for i in range(depth) for n in ("attn.qkv", "attn.proj", "mlp.fc1", "mlp.fc2")]
 
     # ------------------------------------------------------------------ engine plumbing
     def _engine(self, device):
-        if self.flat is None or not self.flat.intact() or self.flat.device != device:
-            self.flat = FlatParams(self, device)
+        if ensure_flat(self, device, transposed=self._t_names,
+                       sentinels=("cls_token", "patch_embed.proj.weight", "blocks.0.attn.qkv.weight", "norm.weight",
+                                  f"blocks.{self.depth - 1}.mlp.fc2.weight")):
             self._anchor = torch.zeros(1, device=device, requires_grad=True)
-            self._sig = None
-        sig = self.flat.signature(self._sentinels)
-        if sig != self._sig:
-            self.flat.refresh_shadows(self._t_names)
-            self._sig = self.flat.signature(self._sentinels)
+        self.flat.fresh()
         return self.flat
 
-    def shadows_dirty(self):
-        self._sig = None
-
     def load_state_dict(self, *a, **k):
-        r = super().load_state_dict(*a, **k)
-        self._sig = None
-        return r
+        if self.flat is not None:
+            self.flat.mark_dirty()
+        return super().load_state_dict(*a, **k)
 
     def sgd_step(self, lr, grad_scale=1.0):
         """Fused vanilla SGD over the whole flat buffer (prepare_model.py:566-567) + shadow refresh."""
-        self.flat.sgd_step(lr, grad_scale, self._t_names)
-        self._sig = self.flat.signature(self._sentinels)
+        self.flat.sgd_step(lr, grad_scale)
 
     def block_grad_range(self, i):
         """[lo, hi) slice of the flat gradient buffer that belongs to block i."""

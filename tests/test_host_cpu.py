@@ -519,3 +519,58 @@ def test_feature_extractor_shapes_per_remainder():
     for left, want in ((300, (256, 256, 256, 256)), (256, (256, 256, 256, 256)), (255, (256, 64, 256, 256)),
                        (100, (256, 64, 100, 104)), (34, (256, 64, 34, 40)), (33, (256, 64, 34, 40)), (1, (256, 64, 2, 8))):
         assert (one.shape_for(left), fixed.shape_for(left), fit.shape_for(left), fit8.shape_for(left)) == want, left
+
+
+def test_shadow_freshness_launches(monkeypatch):
+    """When are the weight shadows (bf16 / fp32 copies and pre-transposed weights the kernels read) refreshed?  On the first
+    `_engine` call, not on the second, again after an in-place edit of a sentinel parameter, after load_state_dict and after a
+    parameter was re-pointed away from the flat buffer (`intact()` false: the buffer is rebuilt); a fused SGD step relaunches the
+    transposes once and leaves nothing for the next `_engine` call.  A missed refresh is silent wrong numbers, so the launches
+    are pinned here: `sais_amd._lib.call` is replaced by a recorder (no library, no GPU) and the engines run on 'cpu'.
+    `weights_key()` (what graph caches compare) moves with every one of those events and with nothing else."""
+    from types import SimpleNamespace
+    from sais_amd import _lib
+    from sais_amd.dino import DINOHead
+    from sais_amd.temporal import fullModel
+    from sais_amd.vit import vit_small
+    calls = []
+    monkeypatch.setattr(_lib, "call", lambda name, *a: calls.append(name) or 0)
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a: SimpleNamespace(cuda_stream=0))
+    monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True))      # the wrappers refuse host tensors
+    cpu = torch.device("cpu")
+    head_tail = ["sais_weight_norm_fwd", "sais_transpose_f32", "sais_split_bf16x3"]
+    for m, sentinel, refresh in ((vit_small(depth=2), "norm.weight", ["sais_cast_bf16", "sais_transpose_batch"]),
+                                 (fullModel('reps', 2, 'NH_02', 384, 'ViT'), "frame_cls", ["sais_transpose_batch"]),
+                                 (DINOHead(384, 256, hidden_dim=256, bottleneck_dim=128), "mlp.4.bias",
+                                  ["sais_transpose_batch"] + head_tail)):
+        def engine():
+            del calls[:]
+            fl = m._engine(cpu)
+            assert fl is m.flat and fl.intact()
+            return list(calls), fl.weights_key()
+
+        first, k0 = engine()
+        assert first == refresh, (type(m).__name__, first)
+        again, k1 = engine()
+        assert again == [] and k1 == k0
+        with torch.no_grad():
+            dict(m.named_parameters())[sentinel].mul_(1.0)
+        edited, k2 = engine()
+        assert edited == refresh and k2 != k1
+        assert engine() == ([], k2)
+        m.load_state_dict({k: v.clone() for k, v in m.state_dict().items()})
+        loaded, k3 = engine()
+        assert loaded == refresh and k3 != k2
+        old = m.flat
+        p = next(m.parameters())
+        p.data = p.data.clone()
+        assert not old.intact()
+        rebuilt, k4 = engine()
+        assert rebuilt == refresh and m.flat is not old and k4 not in (k0, k1, k2, k3)
+        assert engine() == ([], k4)
+        if hasattr(m, "sgd_step"):
+            del calls[:]
+            m.sgd_step(0.1)
+            assert calls == ["sais_sgd_step", "sais_transpose_batch"]
+            assert engine()[0] == [] and m.flat.weights_key() != k4
+            assert engine() == ([], m.flat.weights_key())
