@@ -736,6 +736,31 @@ int sais_grad_norms(const float* grad, const SaisOptChunk* chunks, int nchunks, 
                     float scale, float* partial_ws, float* norms, void* stream);
 int sais_adamw_ema_step(const SaisAdamW* a, void* stream);
 
+/* ================================================================ weighted k-NN evaluation (dino-main/eval_knn.py:143-182)
+ * The frozen-feature classifier without the [Nq, Nt] similarity matrix (sais_amd/csrc/knn.hip, host: sais_amd/knn.py).
+ * sais_knn_search: test f32 [Nq, D] and train [Nt, D], rows L2-normalised; train is f32, or with train_is_split != 0 the
+ *   bf16 [Nt, 3 D] B-side image of sais_split_bf16x3 (an index is split once and reused; both forms give the same bits).
+ *   Writes the kmax largest dot products of every test row, val f32 [Nq, kmax] and idx i32 [Nq, kmax], sorted by
+ *   (value descending, train index ascending); the same order decides which of several equal values are kept at the cut.
+ *   Arithmetic: bf16x3 on the matrix cores, one K order for every pair, no atomics: duplicate train rows get bit-equal
+ *   values and a call is bit-reproducible.  1 <= kmax <= SAIS_KNN_MAX_K, kmax <= Nt, D % 64 == 0, D <= SAIS_KNN_MAX_DIM;
+ *   any Nq >= 1 and Nt.  workspace: sais_knn_workspace_bytes(Nq, Nt, kmax) bytes (candidate lists per test row and train
+ *   split; it does not grow with Nt once the split count has reached its cap).
+ * sais_knn_vote: for each of ks[0] < ... < ks[m-1] <= kmax (host array, m <= SAIS_KNN_MAX_KS)
+ *   votes_j[c] = sum over the first ks[j] neighbours n with train_labels[idx[n]] == c of expf(val[n] / T), added in fp32
+ *   in neighbour order; pred i32 [m, Nq, 5] = the five best classes by (vote descending, class ascending), which is
+ *   torch.sort(descending=True) on the CPU; votes f32 [m, Nq, num_classes] is written when not NULL.
+ *   num_classes <= SAIS_KNN_MAX_CLASSES.                                                                              */
+#define SAIS_KNN_MAX_K 256
+#define SAIS_KNN_MAX_DIM 1536
+#define SAIS_KNN_MAX_CLASSES 4096
+#define SAIS_KNN_MAX_KS 8
+size_t sais_knn_workspace_bytes(int Nq, int Nt, int kmax);
+int sais_knn_search(const float* test, const void* train, int train_is_split, int Nq, int Nt, int D, int kmax, float* val,
+                    int* idx, void* workspace, size_t workspace_bytes, void* stream);
+int sais_knn_vote(const float* val, const int* idx, int Nq, int kmax, const int* train_labels, int Nt, int num_classes,
+                  float T, const int* ks, int m, int* pred, float* votes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -239,6 +239,12 @@ SIGNATURES = {
     "sais_opt_chunk_elems": [],
     "sais_grad_norms": [c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p],
     "sais_adamw_ema_step": [ctypes.POINTER(SaisAdamW), c_void_p],
+    # weighted k-NN evaluation
+    "sais_knn_workspace_bytes": [c_int, c_int, c_int],
+    "sais_knn_search": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, ctypes.c_size_t,
+                        c_void_p],
+    "sais_knn_vote": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_float, ctypes.POINTER(c_int), c_int, c_void_p,
+                      c_void_p, c_void_p],
 }
 
 _lib = None
@@ -267,6 +273,7 @@ def load():
     lib.sais_jpeg_workspace_bytes.restype = ctypes.c_size_t
     lib.sais_augment_workspace_bytes.restype = ctypes.c_size_t
     lib.sais_gemm_tn_grouped_slab_bytes.restype = ctypes.c_size_t
+    lib.sais_knn_workspace_bytes.restype = ctypes.c_size_t
     lib.sais_last_error.restype = ctypes.c_char_p
     lib.sais_last_error.argtypes = []
     _lib = lib
