@@ -435,6 +435,13 @@ int sais_patchify(const float* frames_f32 /*[F,3,side,side]*/, int frames, int s
                   void* patches_bf16 /*[F*(side/16)^2,768]*/, void* stream);
 int sais_vit_cls_rows(const float* cls, const float* pos0, float* tokens, long frame_stride, int frames, int dim,
                       void* stream);
+/* The classifier input of the linear probe with --avgpool_patchtokens (dino-main/eval_linear.py:166-170, n_last_blocks = 1):
+ * x f32 [frames][ntok, dim] (frame_stride floats apart) is the residual stream after the last block; LayerNorm (gamma, beta, eps:
+ * the final self.norm, vision_transformer.py:212) of all ntok rows, then y[f][2 j] = norm(x)[f][0][j] (the CLS token) and
+ * y[f][2 j + 1] = mean over the ntok - 1 patch rows of norm(x)[f][1..][j]: the reference's cat(..., dim=-1).reshape
+ * interleaves.  y f32, ldy >= 2 dim floats between frames.  One workgroup per frame, the patch mean summed in a fixed order. */
+int sais_vit_cls_avgpool_norm(const float* x, long frame_stride, int frames, int ntok, int dim, const float* gamma,
+                              const float* beta, float eps, float* y, long ldy, void* stream);
 /* dcls/dpos += reductions of dtokens f32 [F,ntok,dim]; dpatch_bf16 [F*(ntok-1), dim] = rows 1.. (dY of patch GEMM) */
 int sais_vit_embed_bwd(const float* dtokens, int frames, int ntok, int dim, float* dcls, float* dpos,
                        void* dpatch_bf16, void* stream);
@@ -760,6 +767,45 @@ int sais_knn_search(const float* test, const void* train, int train_is_split, in
                     int* idx, void* workspace, size_t workspace_bytes, void* stream);
 int sais_knn_vote(const float* val, const int* idx, int Nq, int kmax, const int* train_labels, int Nt, int num_classes,
                   float T, const int* ks, int m, int* pred, float* votes, void* stream);
+
+/* ================================================================ linear probe on frozen features (dino-main/eval_linear.py)
+ * H classifier heads (1 <= H <= SAIS_PROBE_MAX_HEADS) that differ only in learning rate are trained from one feature batch
+ * (sais_amd/csrc/probe.hip, host: sais_amd/linear.py).  All tensors f32: X [B, Dm], W [H, C, Dm], b [H, C], Z [H, B, C];
+ * 1 <= B <= SAIS_PROBE_MAX_ROWS, 1 <= C <= SAIS_PROBE_MAX_CLASSES, Dm % 64 == 0, Dm <= SAIS_PROBE_MAX_DIM.  Arithmetic: the
+ * exact f32-input MFMA, one accumulator chain per output element in ascending k; no atomics: bit-reproducible.
+ * sais_probe_logits: Z[h] = X W[h]^T + b[h] (LinearClassifier.forward, eval_linear.py:246-251).  A row's logits do not
+ *   depend on B, on the row's position or on H.
+ * sais_probe_ce: nn.CrossEntropyLoss with mean reduction (eval_linear.py:176, :216) per (head, row): loss_rows f32 [H, B] =
+ *   lse - z[target]; top5 i32 [H, B, 5] (NULL allowed with train) = the five best classes by (logit descending, class
+ *   ascending), slots >= C hold -1 (utils.accuracy, eval_linear.py:218-221); with train != 0, Z is replaced in place by
+ *   dZ = (softmax - onehot) / B.  loss f32 [H] (NULL allowed with train) = mean of loss_rows over the rows, added in row
+ *   order by a second small launch.  targets i32 [B] in [0, C).
+ * sais_probe_update: per 64 x 64 tile of W[h], G = dZ[h]^T X over the B rows in ascending order, then torch.optim.SGD with
+ *   momentum (eval_linear.py:103-108; dampening 0, weight decay 0): m = momentum m + G, W -= lr[h] m; a zero-initialised
+ *   buffer gives torch's first step (buf = grad).  The owners of feature tile 0 do the same for b with db[c] = sum over rows
+ *   of dZ[r][c] in row order.  dW is never stored.  With loss / loss_rows set, loss[h] = mean of loss_rows[h] in row order
+ *   rides in this launch (a training step is then three launches: logits, ce, update).  0 <= momentum < 1, lr[h] >= 0.  */
+#define SAIS_PROBE_MAX_HEADS 8
+#define SAIS_PROBE_MAX_ROWS 1024
+#define SAIS_PROBE_MAX_CLASSES 4096
+#define SAIS_PROBE_MAX_DIM 1920
+typedef struct {
+    const float* X;            /* [B, Dm] */
+    const float* dZ;           /* [H, B, C], from sais_probe_ce in train mode */
+    float* W;                  /* [H, C, Dm] */
+    float* b;                  /* [H, C] */
+    float* mW;                 /* momentum buffers, as W and b */
+    float* mb;
+    const float* loss_rows;    /* [H, B] or NULL */
+    float* loss;               /* [H] or NULL (both or neither) */
+    int H, B, C, Dm;
+    float momentum;
+    float lr[SAIS_PROBE_MAX_HEADS];
+} SaisProbeUpdate;
+int sais_probe_logits(const float* X, const float* W, const float* b, int H, int B, int C, int Dm, float* Z, void* stream);
+int sais_probe_ce(float* Z, const int* targets, int H, int B, int C, int train, float* loss_rows, int* top5, float* loss,
+                  void* stream);
+int sais_probe_update(const SaisProbeUpdate* u, void* stream);
 
 #ifdef __cplusplus
 }

@@ -116,6 +116,12 @@ class SaisAdamW(ctypes.Structure):
                 ("eps", c_float), ("bc1", c_float * 2), ("sqrt_bc2", c_float * 2), ("frozen1", c_int), ("ema_m", c_float), ("grad_scale", c_float)]
 
 
+class SaisProbeUpdate(ctypes.Structure):
+    _fields_ = [("X", c_void_p), ("dZ", c_void_p), ("W", c_void_p), ("b", c_void_p), ("mW", c_void_p), ("mb", c_void_p),
+                ("loss_rows", c_void_p), ("loss", c_void_p), ("H", c_int), ("B", c_int), ("C", c_int), ("Dm", c_int),
+                ("momentum", c_float), ("lr", c_float * 8)]
+
+
 OPT_DECAY, OPT_CLASS1, OPT_NO_GRAD = 1, 2, 4
 
 EPI_BIAS_BF16, EPI_BIAS_RELU_BF16, EPI_BIAS_F32, EPI_BIAS_RESID_F32 = 0, 1, 2, 3
@@ -170,6 +176,7 @@ SIGNATURES = {
     "sais_im2col_f32": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p],
     "sais_patchify": [c_void_p, c_int, c_int, c_void_p, c_void_p],
     "sais_vit_cls_rows": [c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_void_p],
+    "sais_vit_cls_avgpool_norm": [c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_long, c_void_p],
     "sais_vit_embed_bwd": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "sais_sgd_step": [c_void_p, c_void_p, c_void_p, c_long, c_float, c_float, c_void_p],
     "sais_cast_bf16": [c_void_p, c_void_p, c_long, c_void_p],
@@ -245,6 +252,10 @@ SIGNATURES = {
                         c_void_p],
     "sais_knn_vote": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_float, ctypes.POINTER(c_int), c_int, c_void_p,
                       c_void_p, c_void_p],
+    # linear probe
+    "sais_probe_logits": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
+    "sais_probe_ce": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "sais_probe_update": [ctypes.POINTER(SaisProbeUpdate), c_void_p],
 }
 
 _lib = None

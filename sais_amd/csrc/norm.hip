@@ -158,7 +158,60 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16* dy16, long lddy
         }
     }
 }
+
+// probe_features(avgpool=True) (eval_linear.py:166-170 with n = 1): one workgroup per frame normalises all its token rows;
+// y[2 j] = norm(x)[0][j] (CLS), y[2 j + 1] = mean over the patch rows of norm(x)[1..][j].  Half-wave w adds its rows
+// w, w + 8, ... in ascending order, the eight partial sums are added in half-wave order: a fixed order, no atomics.
+__global__ __launch_bounds__(256) void cls_avgpool_norm_kernel(const float* x, long frame_stride, int ntok, const float* gamma,
+                                                               const float* beta, float eps, float* y, long ldy) {
+    __shared__ float red[8][D];
+    const int l32 = threadIdx.x & 31, hw = threadIdx.x >> 5;
+    const float* xf = x + (size_t)blockIdx.x * frame_stride;
+    float* yf = y + (size_t)blockIdx.x * ldy;
+    float gm[12], bt[12], acc[12];
+    load_f32(gamma, l32, gm);
+    load_f32(beta, l32, bt);
+#pragma unroll
+    for (int i = 0; i < 12; ++i) acc[i] = 0.f;
+    for (int row = hw; row < ntok; row += 8) {
+        float v[12];
+        load_f32(xf + (size_t)row * D, l32, v);
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < 12; ++i) s += v[i];
+        const float mu = half_sum(s) * (1.0f / D);
+        float q = 0.f;
+#pragma unroll
+        for (int i = 0; i < 12; ++i) { float d = v[i] - mu; q += d * d; }
+        const float rs = rsqrtf(half_sum(q) * (1.0f / D) + eps);
+#pragma unroll
+        for (int i = 0; i < 12; ++i) {
+            v[i] = (v[i] - mu) * rs * gm[i] + bt[i];
+            if (row == 0) yf[2 * col_of(l32, i)] = v[i];
+            else acc[i] += v[i];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 12; ++i) red[hw][col_of(l32, i)] = acc[i];
+    __syncthreads();
+    for (int c = threadIdx.x; c < D; c += 256) {
+        float s = 0.f;
+#pragma unroll
+        for (int h = 0; h < 8; ++h) s += red[h][c];
+        yf[2 * c + 1] = s / (float)(ntok - 1);
+    }
+}
 }  // namespace
+
+extern "C" int sais_vit_cls_avgpool_norm(const float* x, long frame_stride, int frames, int ntok, int dim, const float* gamma,
+                                         const float* beta, float eps, float* y, long ldy, void* stream) {
+    SAIS_ENTER();
+    if (!x || !gamma || !beta || !y || dim != D || frames <= 0 || ntok < 2 || (frame_stride & 3)) return SAIS_ERR_ARG;
+    if (frame_stride < (long)ntok * D || ldy < 2 * D) return SAIS_ERR_ARG;
+    hipLaunchKernelGGL(cls_avgpool_norm_kernel, dim3(frames), dim3(256), 0, (hipStream_t)stream, x, frame_stride, ntok, gamma,
+                       beta, eps, y, ldy);
+    return sais_check_launch();
+}
 
 extern "C" int sais_layernorm_fwd(const float* x, long ldx, int rows, int dim, const float* gamma, const float* beta,
                                   float eps, void* y_bf16, long ldy16, float* y_f32, long ldy32, float* mean,

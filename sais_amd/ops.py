@@ -611,6 +611,13 @@ def vit_cls_rows(cls, pos0, tokens, frames, ntok=197):
     L.call("sais_vit_cls_rows", _p(cls), _p(pos0), _p(tokens), ntok * 384, frames, 384, _stream())
 
 
+def vit_cls_avgpool_norm(x, frames, gamma, beta, eps, y, ntok=197):
+    """y f32 [frames, 768]: column 2 j = norm(x)[:, 0, j], column 2 j + 1 = mean over the patch rows of norm(x)[:, 1:, j]."""
+    _chk(x, F32, "x"); _chk(y, F32, "y")
+    L.call("sais_vit_cls_avgpool_norm", _p(x), ntok * 384, frames, ntok, 384, _p(gamma), _p(beta), eps, _p(y), y.stride(0),
+           _stream())
+
+
 def vit_embed_bwd(dtokens, frames, dcls, dpos, dpatch, ntok=197):
     L.call("sais_vit_embed_bwd", _p(dtokens), frames, ntok, 384, _p(dcls), _p(dpos), _p(dpatch), _stream())
 

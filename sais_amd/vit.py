@@ -1,6 +1,6 @@
 """DINO ViT-S/16 spatial encoder on MI355X — drop-in for the reference's
 SAIS/scripts/dino-main/vision_transformer.py (`vit_small`, `VisionTransformer.forward` :209-214,
-`get_last_selfattention` :216-223) with the same parameter names / shapes (150-tensor state_dict,
+`get_last_selfattention` :216-223, `get_intermediate_layers` :225-233) with the same parameter names / shapes (150-tensor state_dict,
 SURVEY App. A), so `dino_deitsmall16_pretrain.pth` loads strictly.
 
 Every block runs as hand-written gfx950 kernels through the C ABI (include/sais_hip.h):
@@ -238,6 +238,62 @@ class VisionTransformer(nn.Module):
         self._engine(x.device)
         return self._forward_kernels(x, save=False, want_last_attn=True)[0]
 
+    @torch.no_grad()
+    def get_intermediate_layers(self, x, n=1):
+        """vision_transformer.py:225-233: norm(x) after each of the last n blocks, oldest first, as n tensors f32
+        [F, 197, 384].  Inference only (runs under no_grad, nothing is saved for a backward); 224 x 224 frames only.  Every row
+        of the last block is computed (no CLS-only tail)."""
+        x = self._check_input(x)
+        if x.shape[-1] != 224:
+            raise ValueError("get_intermediate_layers takes 224 x 224 frames")
+        n = int(n)
+        if not 1 <= n <= self.depth:
+            raise ValueError(f"n = {n} must be in [1, {self.depth}]")
+        f, Fr, out = self._engine(x.device), x.shape[0], []
+
+        def tap(i, xs):            # the residual stream is updated in place: normalise it before the next block runs
+            if i >= self.depth - n:
+                y = torch.empty(Fr, NTOK, D, dtype=torch.float32, device=x.device)
+                ops.layernorm_fwd(xs, Fr * NTOK, D, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6, y32=y)
+                out.append(y)
+        self._forward_kernels(x, save=False, tap=tap, prune=False)
+        return out
+
+    @torch.no_grad()
+    def probe_features(self, x, n=4, avgpool=False):
+        """The classifier input of the linear probe, f32 [F, dim] (eval_linear.py:166-170), inference only.
+        avgpool = False: dim = 384 n, the CLS rows of norm(x) after the last n blocks, oldest first; the last 384 columns are
+        forward()'s output (the CLS-only last block stays in use), each earlier slot is one LayerNorm launch over the strided
+        CLS rows written straight into its columns.  avgpool = True: as the reference, only n = 1 (its torch.cat raises for
+        n > 1), dim = 768 INTERLEAVED: column 2 j is CLS[j], column 2 j + 1 the mean of the patch tokens of norm(x)[j]."""
+        n = int(n)
+        if avgpool and n != 1:
+            raise ValueError("avgpool_patchtokens needs n_last_blocks = 1: the reference's torch.cat (eval_linear.py:169) "
+                             f"cannot join [F, {D * n}, 1] with [F, {D}, 1]")
+        x = self._check_input(x)
+        if x.shape[-1] != 224:
+            raise ValueError("probe_features takes 224 x 224 frames")
+        if not 1 <= n <= self.depth:
+            raise ValueError(f"n = {n} must be in [1, {self.depth}]")
+        f, Fr = self._engine(x.device), x.shape[0]
+        if avgpool:
+            last = []
+            self._forward_kernels(x, save=False, tap=lambda i, xs: last.append(xs) if i == self.depth - 1 else None, prune=False)
+            feats = torch.empty(Fr, 2 * D, dtype=torch.float32, device=x.device)
+            ops.vit_cls_avgpool_norm(last[0], Fr, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6, feats)
+            return feats
+        if n == 1:
+            return self._forward_kernels(x, save=False)[0]
+        feats = torch.empty(Fr, D * n, dtype=torch.float32, device=x.device)
+        first = self.depth - n
+
+        def tap(i, xs):            # slots of the earlier blocks; the last slot is written by the pass itself (reps_out)
+            if first <= i < self.depth - 1:
+                ops.layernorm_fwd(xs, Fr, NTOK * D, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6,
+                                  y32=feats[:, (i - first) * D:], ldy32=D * n)
+        self._forward_kernels(x, save=False, tap=tap, reps_out=feats[:, (n - 1) * D:])
+        return feats
+
     def _check_input(self, x):
         if not x.is_cuda:
             raise L.SaisHipError("VisionTransformer.forward needs a device tensor: the HIP path has no CPU fallback")
@@ -259,12 +315,14 @@ class VisionTransformer(nn.Module):
         return out, Wm
 
     # ------------------------------------------------------------------ forward kernels
-    def _forward_kernels(self, img, save, want_last_attn=False):
+    def _forward_kernels(self, img, save, want_last_attn=False, tap=None, prune=True, reps_out=None):
         """img: one [F,3,S,S] tensor, or a LIST of them with different S (DINO's multi-crop student, utils.py:611-630):
         the groups are then stacked along the token-row axis and every GEMM / LayerNorm of a block runs ONCE over all rows
         (only attention, the embedding glue and the final CLS gather are per group) — 44 160 rows in one launch fill the
         chip where 25 216 + 18 944 in two launches leave workgroup slots empty.  Returns reps f32 [sum F, 384] in group
-        order."""
+        order.  tap(i, x): called after every block but a CLS-only last one with the residual stream the block left (without
+        `save` the next block overwrites it); prune = False: the last block computes every row; reps_out: a [sum F, 384] view
+        (any row stride) that receives reps instead of a new tensor."""
         f = self.flat
         imgs = list(img) if isinstance(img, (list, tuple)) else [img]
         dev = imgs[0].device
@@ -281,7 +339,7 @@ class VisionTransformer(nn.Module):
         # the CLS-only tail runs its [frames, 384] GEMMs on the split-K small-M kernel (SAIS_EPI_RAW_SLABS_F32: M < 8192 only), so a
         # pass with 8192 or more FRAMES computes the last block on every row like the others (pruned=False is
         # recorded in `saved`, the backward follows it)
-        pl.prune = self.prune_last_block and not want_last_attn and Ftot < ops.ROW_GEMM_MIN_M
+        pl.prune = prune and self.prune_last_block and not want_last_attn and Ftot < ops.ROW_GEMM_MIN_M
         pl.prune_q = pl.prune and len(groups) == 1 and _PRUNE_Q
         pl.mlp_fused = ops.mlp_fused_enabled(M)
         # One C call per Block (sais_vit_block_fwd: the launches of _block_fwd_launches, sequenced by the library) whenever
@@ -315,7 +373,7 @@ class VisionTransformer(nn.Module):
                                 qkv.view(g0["Fr"], g0["ntok"], 3 * D)[:, 0, :D], bias=bq[:D])
                 else:
                     ops.gemm_nt(xn, Wq, L.EPI_BIAS_BF16, qkv, bias=bq)
-                reps, tail = self._cls_tail_fwd(f, i, x, *ln1, qkv, groups, dp, save, pl.e16, pl.e32)
+                reps, tail = self._cls_tail_fwd(f, i, x, *ln1, qkv, groups, dp, save, pl.e16, pl.e32, reps_out)
                 if save:
                     saved["blocks"].append(tail)
                     saved.update(x_final=tail["x_out"], meanN=tail["meanN"], rstdN=tail["rstdN"], pruned=True)
@@ -338,7 +396,9 @@ class VisionTransformer(nn.Module):
             if save:
                 saved["blocks"].append(b)
             x, ln1 = x_out, nxt or ln1
-        reps, meanN, rstdN = self._final_norm_fwd(pl, x)
+            if tap is not None:
+                tap(i, x)
+        reps, meanN, rstdN = self._final_norm_fwd(pl, x, reps_out)
         if save:
             saved.update(x_final=x, meanN=meanN, rstdN=rstdN)
         return reps, saved
@@ -428,16 +488,16 @@ class VisionTransformer(nn.Module):
                 ops.gemm_nt(h, f.w(p + "mlp.fc2.weight"), L.EPI_BIAS_RESID_F32, x_out, bias=f.w32(p + "mlp.fc2.bias"),
                             aux=x_mid, rowscale=rs_mlp)
 
-    def _final_norm_fwd(self, pl, x):
+    def _final_norm_fwd(self, pl, x, reps_out=None):
         """The final norm on the CLS rows only (row stride = ntok * 384).  Returns (reps f32 [frames, 384], mean, rstd)."""
         f, Ftot = self.flat, pl.Ftot
-        reps = pl.e32(Ftot, D)
+        reps = pl.e32(Ftot, D) if reps_out is None else reps_out
         meanN, rstdN = (pl.e32(Ftot), pl.e32(Ftot)) if pl.save else (None, None)
         for g in pl.groups:
             fr = g["frames"]
             ops.layernorm_fwd(x[g["rows"]], g["Fr"], g["ntok"] * D, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6,
                               y32=reps[fr], mean=None if meanN is None else meanN[fr],
-                              rstd=None if rstdN is None else rstdN[fr])
+                              rstd=None if rstdN is None else rstdN[fr], ldy32=reps.stride(0))
         return reps, meanN, rstdN
 
     def _block_params(self, i):
@@ -448,7 +508,7 @@ class VisionTransformer(nn.Module):
             self._bp = (key, [ops.vit_block_params(f, j, self.depth) for j in range(self.depth)])
         return self._bp[1][i]
 
-    def _cls_tail_fwd(self, f, i, x, xn1, mean1, rstd1, qkv, groups, dp, save, e16, e32):
+    def _cls_tail_fwd(self, f, i, x, xn1, mean1, rstd1, qkv, groups, dp, save, e16, e32, reps_out=None):
         """The last block from its qkv on, restricted to what forward() returns (the CLS rows): attention for the CLS query
         (sais_vit_attn_cls_fwd, one launch per resolution group), then proj + residual, norm2, fc1 + GELU, fc2 + residual and
         the final norm on [frames, 384] tensors (all groups together).  The residual input is the strided view x[::ntok]."""
@@ -474,9 +534,10 @@ class VisionTransformer(nn.Module):
                     bias=f.w32(p + "mlp.fc1.bias"), out2=u)
         ops.gemm_nt_splitk(h, f.w(p + "mlp.fc2.weight"), 12, bias=f.w32(p + "mlp.fc2.bias"), rowscale=rs_mlp, aux=x_mid,
                            out32=x_out)
-        reps = e32(Ftot, D)
+        reps = e32(Ftot, D) if reps_out is None else reps_out
         meanN, rstdN = (e32(Ftot), e32(Ftot)) if save else (None, None)
-        ops.layernorm_fwd(x_out, Ftot, D, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6, y32=reps, mean=meanN, rstd=rstdN)
+        ops.layernorm_fwd(x_out, Ftot, D, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6, y32=reps, mean=meanN, rstd=rstdN,
+                          ldy32=reps.stride(0))
         tail = dict(cls=True, x_in=x, mean1=mean1, rstd1=rstd1, xn1=xn1, qkv=qkv, ao=ao, x_mid=x_mid, mean2=mean2, rstd2=rstd2,
                     xn2=xn2, dgelu=u, h=h, rs_attn=rs_attn, rs_mlp=rs_mlp, x_out=x_out, meanN=meanN, rstdN=rstdN) if save else None
         return reps, tail
