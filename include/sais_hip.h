@@ -807,6 +807,52 @@ int sais_probe_ce(float* Z, const int* targets, int H, int B, int C, int train, 
                   void* stream);
 int sais_probe_update(const SaisProbeUpdate* u, void* stream);
 
+/* ================================================================ dense ViT features at any resolution
+ * (dino-main/eval_video_segmentation.py runs get_intermediate_layers on 480 x 832 frames: 30 x 52 patches + CLS = 1561 tokens;
+ * sais_amd/csrc/attn_any.hip, host: VisionTransformer.dense_features).  Additive entries: the ABI version does not change.
+ * sais_vit_attn_fwd_any: the layouts and arithmetic contract of sais_vit_attn_fwd (qkv bf16 [frames*ntok, 1152] = q | k | v
+ *   head-major, out bf16 [frames*ntok, 384], fp32 softmax statistics, lse f32 [frames, 6, ntok] optional) for any
+ *   2 <= ntok <= SAIS_VIT_ATTN_ANY_MAX_TOKENS: keys and values stream through LDS in tiles of 64 with an online softmax; keys
+ *   past the end are masked before the row maximum, rows past frames * ntok of `out` are not written.  Forward only, no
+ *   probabilities.  No atomics: bit-reproducible, and a row's result does not depend on the workgroup size the launcher picks.
+ * sais_patchify_rect: frames f32 [F, 3, H, W], H and W multiples of 16 -> patches bf16 [F * (H/16) * (W/16), 768], patch rows
+ *   in row-major order of the (H/16, W/16) grid, the 768 columns in sais_patchify's order (c, py, px).                   */
+#define SAIS_VIT_ATTN_ANY_MAX_TOKENS 4097
+int sais_vit_attn_fwd_any(const void* qkv, long ldqkv, int frames, int ntok, void* out, long ldo, float* lse /*optional*/,
+                          void* stream);
+int sais_patchify_rect(const float* frames_f32 /*[F,3,H,W]*/, int frames, int H, int W, void* patches_bf16, void* stream);
+
+/* ================================================================ video object segmentation: label propagation
+ * (dino-main/eval_video_segmentation.py; sais_amd/csrc/vos.hip, host: sais_amd/vos.py).
+ * sais_vos_propagate: label_propagation (:113-150) for one target frame.  n = h * w <= SAIS_VOS_MAX_PATCHES patches, row-major.
+ *   tar f32 [n, dim] and ctx f32 [nctx, n, dim]: patch features with L2-NORMALISED rows (normalise a frame once, when it enters
+ *   the context: sais_l2norm_fwd); segs f32 [nctx, C, n]: the context frames' soft masks; out f32 [C, n].
+ *   a[c, key, q] = exp(10 cos(q, key_c)) where |y_q - y_key| <= radius and |x_q - x_key| <= radius (everywhere when radius ==
+ *   0), else 0.  Per query q, t = the topk-th largest of the nctx * n values a[., ., q]; every entry with a >= t is kept — ties at
+ *   the threshold ALL stay, and with fewer than topk in-window entries t = 0 keeps every in-window entry.  out[:, q] = the
+ *   average of segs[c, :, key] over the kept entries weighted by a.  Selection is done on the cosines (exp is monotone), which
+ *   are exact-f32 MFMA dot products in one fixed order: identical rows give bit-identical cosines in every context slot.
+ *   1 <= nctx <= SAIS_VOS_MAX_CONTEXT, 1 <= C <= SAIS_VOS_MAX_CLASSES, 1 <= topk <= SAIS_VOS_MAX_TOPK, dim == SAIS_VOS_DIM.
+ *   ctx_order (host array of nctx values in [0, SAIS_VOS_MAX_CONTEXT), or NULL for 0 .. nctx - 1): context c is slot
+ *   ctx_order[c] of ctx and segs, so a ring buffer of frames is read in the reference's order (first frame, then oldest to
+ *   newest) without moving it.  One launch, no workspace, no atomics: bit-reproducible.
+ * sais_vos_upsample_argmax: seg f32 [C, h, w] -> labels u8 [h * patch, w * patch] (:74-76): bilinear upsampling by `patch`
+ *   (align_corners = False: source coordinate (i + 0.5) / patch - 0.5 clamped at 0, neighbours clamped at the border), then per
+ *   channel norm_mask (:102-110) on the UPSAMPLED map (maximum <= 0: left as it is; else minus its minimum, divided by the
+ *   maximum of the shifted map), then the channel argmax per pixel, ties to the lowest channel, a NaN (a constant positive
+ *   channel: 0 / 0) counting as the largest, as torch.max does.  1 <= patch <= 64.  workspace: SAIS_VOS_UPSAMPLE_WS_FLOATS
+ *   floats per channel.  Two launches (partial min / max, then normalise + argmax).                                       */
+#define SAIS_VOS_DIM 384
+#define SAIS_VOS_MAX_CONTEXT 16
+#define SAIS_VOS_MAX_CLASSES 64
+#define SAIS_VOS_MAX_TOPK 16
+#define SAIS_VOS_MAX_PATCHES 4096
+#define SAIS_VOS_UPSAMPLE_WS_FLOATS 128
+int sais_vos_propagate(const float* tar, const float* ctx, const float* segs, int nctx, int C, int h, int w, int dim, int radius,
+                       int topk, const int* ctx_order /*host, optional*/, float* out, void* stream);
+int sais_vos_upsample_argmax(const float* seg, int C, int h, int w, int patch, unsigned char* labels, float* workspace,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -256,6 +256,12 @@ SIGNATURES = {
     "sais_probe_logits": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "sais_probe_ce": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "sais_probe_update": [ctypes.POINTER(SaisProbeUpdate), c_void_p],
+    # dense features at any resolution, video object segmentation
+    "sais_vit_attn_fwd_any": [c_void_p, c_long, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p],
+    "sais_patchify_rect": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
+    "sais_vos_propagate": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int),
+                           c_void_p, c_void_p],
+    "sais_vos_upsample_argmax": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
 }
 
 _lib = None

@@ -367,6 +367,14 @@ def vit_attn_fwd(qkv, frames, out, lse=None, probs=None, ntok=197):
                           _p(probs), _stream()))
 
 
+def vit_attn_fwd_any(qkv, frames, ntok, out, lse=None):
+    """The streaming attention forward (csrc/attn_any.hip): any 2 <= ntok <= 4097, no probabilities."""
+    _chk(qkv, BF16, "qkv"); _chk(out, BF16, "out"); _chk(lse, F32, "lse")
+    _timed("vit_attn_fwd_any", 4.0 * frames * 6 * ntok * ntok * 64, 2 * frames * ntok * 384 * 4,
+           lambda: L.call("sais_vit_attn_fwd_any", _p(qkv), qkv.stride(0), frames, ntok, _p(out), out.stride(0), _p(lse),
+                          _stream()))
+
+
 def vit_attn_bwd(qkv, dout, out, lse, delta_ws, frames, dqkv, ntok=197):
     """out = the forward attention output (bf16 [frames*ntok, 384]) saved by vit_attn_fwd."""
     _chk(out, BF16, "out")
@@ -605,6 +613,13 @@ def patchify(frames_f32, patches):
     """frames f32 [F,3,side,side] -> bf16 [F*(side/16)^2, 768]."""
     _chk(frames_f32, F32, "frames")
     L.call("sais_patchify", _p(frames_f32), frames_f32.shape[0], frames_f32.shape[-1], _p(patches), _stream())
+
+
+def patchify_rect(frames_f32, patches):
+    """frames f32 [F,3,H,W] (H, W multiples of 16) -> bf16 [F*(H/16)*(W/16), 768], patch rows in row-major grid order."""
+    _chk(frames_f32, F32, "frames"); _chk(patches, BF16, "patches")
+    L.call("sais_patchify_rect", _p(frames_f32), frames_f32.shape[0], frames_f32.shape[2], frames_f32.shape[3], _p(patches),
+           _stream())
 
 
 def vit_cls_rows(cls, pos0, tokens, frames, ntok=197):

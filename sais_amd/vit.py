@@ -17,6 +17,8 @@ main_dino.py:658-663, with interpolate_pos_encoding :174-194 as a fixed bicubic 
 rates linspace(0, drop_path_rate, depth); SAIS itself only ever runs the ViT in eval(), extract_representations.py:
 279,340,362) is applied in the epilogues of the residual GEMMs as a per-row scale; the keep draws come from Philox
 (`drop_path_seed`, this library's stream, not torch's): `last_droppath_scales` holds what a forward used.
+`dense_features` alone takes other resolutions (any H x W in multiples of 16 up to 4097 tokens, inference only): its attention
+streams keys and values through LDS (csrc/attn_any.hip) instead of keeping a head resident.
 """
 import math
 import os
@@ -33,6 +35,7 @@ from .flat import ensure_flat
 D, NTOK, HEADS, HID, PATCH_K = 384, 197, 6, 1536, 768
 _PRUNE_Q = os.environ.get("SAIS_VIT_PRUNE_Q", "1") != "0"     # the CLS-only last block computes q for the CLS rows only
 SIDES = {224: 197, 96: 37}          # supported frame sizes -> tokens (the attention kernels are instantiated per count)
+MAX_DENSE_TOKENS = 4097             # dense_features: the streaming attention (sais_vit_attn_fwd_any) takes any count up to this
 
 
 def _cubic_taps(t, A=-0.75):
@@ -195,7 +198,7 @@ class VisionTransformer(nn.Module):
                 nn.init.constant_(m.weight, 1.0)
         self.flat = None
         self._anchor = None
-        self._interp = {}                            # frame side -> device f32 [ntok - 1, 196] bicubic map
+        self._interp = {}                            # frame side, or (H, W) of dense_features -> device f32 [ntok - 1, 196] bicubic map
         self.grad_ready_hook = None                  # callable(lo, hi): flat-grad slice [lo,hi) is final
         self._t_names = [f"blocks.{i}.{n}.weight" for i in range(depth) for n in ("attn.qkv", "attn.proj", "mlp.fc1", "mlp.fc2")]
 
@@ -293,6 +296,77 @@ class VisionTransformer(nn.Module):
                                   y32=feats[:, (i - first) * D:], ldy32=D * n)
         self._forward_kernels(x, save=False, tap=tap, reps_out=feats[:, (n - 1) * D:])
         return feats
+
+    @torch.no_grad()
+    def dense_features(self, x, n=1):
+        """get_intermediate_layers (vision_transformer.py:225-233) at ANY resolution: x f32 [F, 3, H, W] on the device, H and W
+        multiples of 16 (not necessarily equal), 1 + (H/16)(W/16) <= 4097 tokens.  Returns n tensors f32 [F, 1 + hw, 384],
+        oldest first: norm(x) after each of the last n blocks.  Inference only, every row of every block is computed.  Its own
+        launch list: patchify_rect, the patch GEMM with the positional table interpolated to (H, W)
+        (interpolate_pos_encoding :174-194), then per block the row-generic GEMM / LayerNorm kernels around the streaming
+        attention (sais_vit_attn_fwd_any).  A 224 x 224 input takes this path too (dino-main/eval_video_segmentation.py runs it
+        at 480 x 832: 1561 tokens)."""
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise L.SaisHipError("VisionTransformer.dense_features needs a device tensor: the HIP path has no CPU fallback")
+        if x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1 or x.shape[2] < 16 or x.shape[3] < 16 or x.shape[2] % 16 or x.shape[3] % 16:
+            raise ValueError(f"expected [F,3,H,W] with H and W positive multiples of 16, got {tuple(x.shape)}")
+        Fr, H, W = x.shape[0], x.shape[2], x.shape[3]
+        ntok = 1 + (H // 16) * (W // 16)
+        if ntok > MAX_DENSE_TOKENS:
+            raise ValueError(f"{H} x {W} frames are {ntok} tokens; at most {MAX_DENSE_TOKENS}")
+        n = int(n)
+        if not 1 <= n <= self.depth:
+            raise ValueError(f"n = {n} must be in [1, {self.depth}]")
+        x = x.contiguous().float()
+        f, dev = self._engine(x.device), x.device
+        M = Fr * ntok
+        e16, e32 = _empty(torch.bfloat16, dev), _empty(torch.float32, dev)
+        patches, xs = e16(Fr * (ntok - 1), PATCH_K), e32(M, D)
+        ops.patchify_rect(x, patches)
+        pos = self._dense_pos_table(H, W, dev)
+        ops.gemm_nt(patches, f.w("patch_embed.proj.weight").view(D, PATCH_K), L.EPI_PATCH_F32, xs.view(Fr, ntok, D),
+                    bias=f.w32("patch_embed.proj.bias"), aux=pos, grp=(ntok - 1, ntok, 1))
+        ops.vit_cls_rows(f.w32("cls_token"), pos, xs.view(Fr, ntok, D), Fr, ntok)
+        fused = M >= ops.ROW_GEMM_MIN_M               # LayerNorm in the epilogue of the N = 384 GEMMs, as _forward_kernels
+        xn, qkv, ao, xn2, h = e16(M, D), e16(M, 3 * D), e16(M, D), e16(M, D), e16(M, HID)
+        out = []
+        for i in range(self.depth):
+            p, last = f"blocks.{i}.", i == self.depth - 1
+            if i == 0 or not fused:
+                ops.layernorm_fwd(xs, M, D, f.w32(p + "norm1.weight"), f.w32(p + "norm1.bias"), 1e-6, y16=xn)
+            ops.gemm_nt(xn, f.w(p + "attn.qkv.weight"), L.EPI_BIAS_BF16, qkv, bias=f.w32(p + "attn.qkv.bias"))
+            ops.vit_attn_fwd_any(qkv, Fr, ntok, ao)
+            if fused:
+                ops.gemm_ln_fwd(ao, f.w(p + "attn.proj.weight"), f.w32(p + "attn.proj.bias"), xs, xs, xn2,
+                                f.w32(p + "norm2.weight"), f.w32(p + "norm2.bias"), 1e-6)
+            else:
+                ops.gemm_nt(ao, f.w(p + "attn.proj.weight"), L.EPI_BIAS_RESID_F32, xs, bias=f.w32(p + "attn.proj.bias"), aux=xs)
+                ops.layernorm_fwd(xs, M, D, f.w32(p + "norm2.weight"), f.w32(p + "norm2.bias"), 1e-6, y16=xn2)
+            ops.gemm_nt(xn2, f.w(p + "mlp.fc1.weight"), L.EPI_BIAS_GELU_BF16, h, bias=f.w32(p + "mlp.fc1.bias"))
+            if fused and not last:
+                q = f"blocks.{i + 1}."
+                ops.gemm_ln_fwd(h, f.w(p + "mlp.fc2.weight"), f.w32(p + "mlp.fc2.bias"), xs, xs, xn,
+                                f.w32(q + "norm1.weight"), f.w32(q + "norm1.bias"), 1e-6)
+            else:
+                ops.gemm_nt(h, f.w(p + "mlp.fc2.weight"), L.EPI_BIAS_RESID_F32, xs, bias=f.w32(p + "mlp.fc2.bias"), aux=xs)
+            if i >= self.depth - n:                   # the stream is updated in place: normalise it before the next block
+                y = e32(Fr, ntok, D)
+                ops.layernorm_fwd(xs, M, D, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6, y32=y)
+                out.append(y)
+        return out
+
+    def _dense_pos_table(self, H, W, dev):
+        """The positional table f32 [1 + (H/16)(W/16), 384] of H x W frames; the bicubic map is cached per (H, W)."""
+        pos = self.flat.w32("pos_embed").view(NTOK, D)
+        if H == W == 224:
+            return pos
+        Wm = self._interp.get((H, W))
+        if Wm is None or Wm.device != dev:
+            Wm = torch.from_numpy(pos_interp_matrix(14, H, W).astype(np.float32)).to(dev)
+            self._interp[(H, W)] = Wm
+        out = torch.empty(1 + Wm.shape[0], D, dtype=torch.float32, device=dev)
+        ops.pos_interp_fwd(Wm, pos, out)
+        return out
 
     def _check_input(self, x):
         if not x.is_cuda:
