@@ -181,8 +181,12 @@ def test_pos_interp_kernels(ops):
 
 
 # ------------------------------------------------------------------ 37-token ViT
-def test_attention_37_tokens(ops):
-    frames = 70                                                      # 420 problems: more than one pass of the backward
+@pytest.mark.parametrize("frames", [70, 129])
+def test_attention_37_tokens(ops, frames):
+    """The backward's persistent grid for 37 tokens is capped at 256 x 3 = 768 workgroups (attn_vit.hip launch_bwd: three
+    43.5-KB workgroups fit the LDS of a CU).  70 frames = 420 problems run in ONE pass; 129 frames = 774 problems is the
+    smallest count past the cap, so six workgroups take a second problem (main_dino.py at batch 64 with 8 local crops runs
+    3072 problems: four passes)."""
     qkv = (rnd(frames * 37, 1152, seed=30, scale=1.5)).to(torch.bfloat16)
     out = torch.empty(frames * 37, 384, dtype=torch.bfloat16, device=DEV)
     lse = torch.empty(frames, 6, 37, device=DEV)
