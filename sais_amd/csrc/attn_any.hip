@@ -9,32 +9,12 @@
 // four lane groups) and P^T is already the B operand of O^T += V^T P^T.  Online softmax: when a tile raises the maximum the
 // accumulators and the running sum are rescaled by exp2((m_old - m_new) c).  No atomics: bit-reproducible, and a query's result
 // does not depend on the workgroup size chosen by the launcher.
-#include "common.hpp"
+#include "attn_frag.hpp"
 #include "../../include/sais_hip.h"
 
 namespace {
-constexpr int HD = 64, NH = 6, DM = 384;
-constexpr int ROWB = 160;                 // LDS row stride in bytes
 constexpr int KT = 64;                    // keys per tile
 constexpr int MAT_BYTES = KT * ROWB;
-constexpr float LOG2E = 1.4426950408889634f;
-
-DEVINL bf16x8 row_frag(const char* lds, int row, int chunk) { return *(const bf16x8*)(lds + row * ROWB + chunk * 16); }
-// transposed fragment for k-step s (32 keys of the tile) and 16-wide column tile ct:
-// element e of lane group g  <->  key 32 s + 16 (e >> 2) + 4 g + (e & 3)
-DEVINL bf16x8 tr_frag(const char* lds, int s, int ct, int g, int li) {
-    const char* p = lds + (32 * s + 4 * g + (li >> 2)) * ROWB + (16 * ct + 4 * (li & 3)) * 2;
-    return cat4(lds_read_tr16(p), lds_read_tr16(p + 16 * ROWB));
-}
-DEVINL float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-DEVINL float group_max(float v) { v = fmaxf(v, __shfl_xor(v, 16)); return fmaxf(v, __shfl_xor(v, 32)); }
-DEVINL float group_sum(float v) { v += __shfl_xor(v, 16); return v + __shfl_xor(v, 32); }
-DEVINL bf16x8 pack_p(const f32x4& a, const f32x4& b) {
-    bf16x8 r;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { r[i] = (bf16)a[i]; r[4 + i] = (bf16)b[i]; }
-    return r;
-}
 
 // grid (query tiles of 16 NW, heads, frames); NW waves of 16 queries each
 template <int NW>

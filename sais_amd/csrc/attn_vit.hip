@@ -12,14 +12,10 @@
 // Orientation: scores are computed transposed, S^T = K Q^T (key on accumulator rows, query on the
 // lane), so that P^T is already the B operand of O^T = V^T P^T with no lane movement; the k-slot
 // map of that product is  element e of lane group g  <->  key 32 s + 16 (e>>2) + 4 g + (e&3).
-#include "common.hpp"
+#include "attn_frag.hpp"
 #include "../../include/sais_hip.h"
 
 namespace {
-constexpr int HD = 64, NH = 6, DM = 384;
-constexpr int ROWB = 160;                 // LDS row stride in bytes
-constexpr float LOG2E = 1.4426950408889634f;
-
 // Token-count geometry.  197 = 224 x 224 frames (the SAIS extraction / training path and DINO's global crops);
 // 37 = DINO's 96 x 96 local crops (main_dino.py:658-663 -> prepare_tokens, vision_transformer.py:196-207).
 template <int NTOK_>
@@ -57,17 +53,6 @@ DEVINL void stage_two(char* lds0, const bf16* src0, char* lds1, const bf16* src1
         *(u32x4*)(lds1 + r * ROWB + c * 16) = r < G::NTOK ? v1[i] : z;
     }
 }
-DEVINL bf16x8 row_frag(const char* lds, int row, int chunk) { return *(const bf16x8*)(lds + row * ROWB + chunk * 16); }
-
-// transposed fragment for k-step s (32 tokens) and 16-wide column tile ct
-DEVINL bf16x8 tr_frag(const char* lds, int s, int ct, int g, int li) {
-    const char* p = lds + (32 * s + 4 * g + (li >> 2)) * ROWB + (16 * ct + 4 * (li & 3)) * 2;
-    return cat4(lds_read_tr16(p), lds_read_tr16(p + 16 * ROWB));
-}
-
-// raw v_exp_f32 (exp2f() adds a denormal-range fix-up of 4 VALU per element; arguments here are <= ~0 and a
-// flush to zero of results below 2^-126 is exactly what softmax wants)
-DEVINL float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
 // NKT sixteen-row tiles over 4 waves: wave w takes tiles w, w+4, ... (NKT / 4 each); the NKT % 4 left-over tiles go to
 // the waves (w - extra) & 3 = 0, 1, ..: `extra` rotates with the (frame, head) index so no SIMD is systematically the last
@@ -75,16 +60,6 @@ DEVINL float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 template <class G> DEVINL int tiles_of_wave(int wid, int extra) { return G::NKT / 4 + ((((wid - extra) & 3) < G::NKT % 4) ? 1 : 0); }
 template <class G> DEVINL int tile_id(int wid, int i, int extra) {
     return i < G::NKT / 4 ? wid + 4 * i : 4 * (G::NKT / 4) + ((wid - extra) & 3);
-}
-
-DEVINL float group_max(float v) { v = fmaxf(v, __shfl_xor(v, 16)); return fmaxf(v, __shfl_xor(v, 32)); }
-DEVINL float group_sum(float v) { v += __shfl_xor(v, 16); return v + __shfl_xor(v, 32); }
-
-DEVINL bf16x8 pack_p(const f32x4& a, const f32x4& b) {
-    bf16x8 r;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { r[i] = (bf16)a[i]; r[4 + i] = (bf16)b[i]; }
-    return r;
 }
 
 // S^T strip for one 16-query tile: s[t][r] = score(key 16 t + 4 g + r, query q0 + li), masked to -inf past 197
@@ -381,9 +356,6 @@ __global__ __launch_bounds__(G::BWD_THREADS) void attn_bwd_kernel(const bf16* qk
     }
 }
 
-#ifndef SAIS_EXPERIMENTAL
-#define SAIS_EXPERIMENTAL 0
-#endif
 #if SAIS_EXPERIMENTAL
 // ------------------------------------------------------------------------------------------ backward without the barrier chain (round 6)
 // EXPERIMENT RECORD (built only with -DSAIS_EXPERIMENTAL=1; SAIS_ATTN_BWD_NB=1 selects it): correct at the first run and 5-7 % SLOWER than

@@ -1,4 +1,6 @@
-// Shared device helpers for the gfx950 (CDNA4 / MI355X) kernels of the SAIS hot path.
+// Shared device helpers for the gfx950 (CDNA4 / MI355X) kernels of the SAIS hot path: vector types, the MFMA wrappers, the bf16x3
+// split, wave / half-wave / DPP-row reductions, the ranked-list order and the wave-wide five-best, GELU, the GEMM tile swizzle.
+// Blocks of one kernel family live beside it: f32x3_tile.hpp, row384.hpp, attn_frag.hpp, gemm_nt_tile.hpp, gemm_row_epi.hpp.
 // Wave = 64 lanes; MFMA = v_mfma_f32_16x16x32_bf16 (fp32 accumulate) unless stated otherwise.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -37,6 +39,22 @@ DEVINL bf16x8 cat4(bf16x4 a, bf16x4 b) {
     return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
+// the exact f32-input MFMA (v_mfma_f32_16x16x4_f32): bit for bit an fmaf chain in ascending k
+DEVINL f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+
+// "bf16x3": eight fp32 values -> hi = bf16(x) and lo = bf16(x - hi), each as one 16-B LDS chunk.  The one definition of the
+// split behind sais_gemm_nt_f32, sais_tgemm and sais_knn_search, which promise each other the same arithmetic
+DEVINL void split8(const f32x4& a, const f32x4& b, u32x4& hi, u32x4& lo) {
+    bf16x8 h, l;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        h[i] = (bf16)a[i]; l[i] = (bf16)(a[i] - (float)h[i]);
+        h[4 + i] = (bf16)b[i]; l[4 + i] = (bf16)(b[i] - (float)h[4 + i]);
+    }
+    hi = __builtin_bit_cast(u32x4, h);
+    lo = __builtin_bit_cast(u32x4, l);
+}
+
 DEVINL bf16x8 zero8() {
     bf16x8 z;
 #pragma unroll
@@ -53,6 +71,39 @@ DEVINL float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
     return v;
+}
+DEVINL float half_sum(float v) {          // reduce over the 32 lanes of a half-wave
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// the order of every ranked list (k-NN neighbours, top-5 classes): value descending, index ascending
+DEVINL bool before(float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai < bi); }
+
+// one wave: the five best of the C floats v[] (LDS) in that order; lane 0 writes their indices to out[0..4], -1 past the last class
+DEVINL void wave_best5(const float* v, int C, int lane, int* out) {
+    int chosen[5];
+#pragma unroll
+    for (int q = 0; q < 5; ++q) {
+        float bv = -INFINITY;
+        int bc = 0x7fffffff;
+        for (int c = lane; c < C; c += 64) {
+            bool taken = false;
+#pragma unroll
+            for (int u = 0; u < q; ++u) taken |= chosen[u] == c;
+            const float w = v[c];
+            if (!taken && before(w, c, bv, bc)) { bv = w; bc = c; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(bv, o);
+            const int oc = __shfl_xor(bc, o);
+            if (before(ov, oc, bv, bc)) { bv = ov; bc = oc; }
+        }
+        chosen[q] = bc;
+        if (lane == 0) out[q] = bc == 0x7fffffff ? -1 : bc;
+    }
 }
 
 // exact-erf GELU (nn.GELU(), vision_transformer.py:49-65) without libm's erff: Abramowitz-Stegun 7.1.26,

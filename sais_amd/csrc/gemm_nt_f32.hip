@@ -5,6 +5,7 @@
 // so 3x the MFMA work is irrelevant.  Single LDS stage (4 x 16 KiB), same swizzle / operand swap /
 // 16-contiguous-columns-per-lane epilogue as the bf16 kernel.
 #include "gemm_nt_tile.hpp"
+#include "f32x3_tile.hpp"
 #include "philox.hpp"
 
 namespace {
@@ -54,20 +55,9 @@ DEVINL void epilogue_f32(const NtParams& p, int m, int n, const float (&v)[16]) 
     }
 }
 
-DEVINL void split8(const f32x4& a, const f32x4& b, u32x4& hi, u32x4& lo) {
-    bf16x8 h, l;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        h[i] = (bf16)a[i]; l[i] = (bf16)(a[i] - (float)h[i]);
-        h[4 + i] = (bf16)b[i]; l[4 + i] = (bf16)(b[i] - (float)h[4 + i]);
-    }
-    hi = __builtin_bit_cast(u32x4, h);
-    lo = __builtin_bit_cast(u32x4, l);
-}
-
 template <int EPI>
 __global__ __launch_bounds__(256) void gemm_nt_f32x3_kernel(NtParams p) {
-    __shared__ __attribute__((aligned(16))) char smem[4 * TILE_BYTES];      // A_hi | A_lo | B_hi | B_lo
+    __shared__ __attribute__((aligned(16))) char smem[F32X3_LDS_BYTES];      // A_hi | A_lo | B_hi | B_lo
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int wr = wid >> 1, wc = wid & 1, g = lane >> 4, li = lane & 15;
     const int n0 = blockIdx.x * BN, m0 = blockIdx.y * BM;
@@ -91,14 +81,9 @@ __global__ __launch_bounds__(256) void gemm_nt_f32x3_kernel(NtParams p) {
     auto lstore = [&]() {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            int r = sr + 32 * i;
             u32x4 hi, lo;
-            split8(ra[i][0], ra[i][1], hi, lo);
-            *(u32x4*)(smem + swz(r, sc)) = hi;
-            *(u32x4*)(smem + TILE_BYTES + swz(r, sc)) = lo;
             split8(rb[i][0], rb[i][1], hi, lo);
-            *(u32x4*)(smem + 2 * TILE_BYTES + swz(perm_row(r), sc)) = hi;
-            *(u32x4*)(smem + 3 * TILE_BYTES + swz(perm_row(r), sc)) = lo;
+            f32x3_store_row(smem, sr + 32 * i, sc, ra[i][0], ra[i][1], hi, lo);
         }
     };
     f32x4 acc[4][4];
@@ -115,28 +100,7 @@ __global__ __launch_bounds__(256) void gemm_nt_f32x3_kernel(NtParams p) {
         lstore();
         __syncthreads();
         if (kt + 1 < nk) gload((kbeg + kt + 1) * BK);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            bf16x8 ah[4], al[4], bh[4], bl[4];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                int oa = swz(wr * 64 + t * 16 + li, ks * 4 + g), ob = swz(wc * 64 + t * 16 + li, ks * 4 + g);
-                ah[t] = *(const bf16x8*)(smem + oa);
-                al[t] = *(const bf16x8*)(smem + TILE_BYTES + oa);
-                bh[t] = *(const bf16x8*)(smem + 2 * TILE_BYTES + ob);
-                bl[t] = *(const bf16x8*)(smem + 3 * TILE_BYTES + ob);
-            }
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt) {
-                    f32x4 c = acc[mt][nt];
-                    c = mfma16(bl[nt], ah[mt], c);
-                    c = mfma16(bh[nt], al[mt], c);
-                    c = mfma16(bh[nt], ah[mt], c);
-                    acc[mt][nt] = c;
-                }
-        }
+        f32x3_kstep(smem, wr, wc, g, li, acc);
     }
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) {

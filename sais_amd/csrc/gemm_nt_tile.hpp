@@ -1,5 +1,6 @@
 // Shared by the 128 x 128 NT GEMMs of gemm.hip, gemm_nt_exp.hip and gemm_nt_f32.hip.  Device: tile constants and the 16-columns-per-
 // lane epilogue of the four-wave (2 x 2 waves of 64 x 64) tile.  Host (end of file): what sais_gemm_nt and sais_gemm_nt_exp_ share.
+// The bf16x3 stage of gemm_nt_f32.hip (LDS image, K step) is in f32x3_tile.hpp, shared with knn.hip.
 #pragma once
 #include "gemm_nt_epi.hpp"
 

@@ -77,11 +77,6 @@ DEVINL void row_epilogue(const RowParams& p, f32x4 (&acc)[RMT][6], char* smem, i
                 *(bf16x4*)(q + 128 * i + 4 * l32) = t;
             }
         };
-        auto half_sum = [&](float v) {
-#pragma unroll
-            for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o);
-            return v;
-        };
         // slab s = local row tiles 2 s, 2 s + 1 of EVERY half (the last slab: local tile 6): slab rows 32 h .. 32 h + 31
         // belong to half h, so all waves free their accumulators at the same pace
         auto dump = [&](int s) {

@@ -11,13 +11,12 @@
 // which also raises the threshold.  Order everywhere is (value descending, train index ascending); tiles stream in index
 // order, so a later column that only EQUALS the threshold loses the tie and the strict compare is exact.  A second launch
 // merges the splits.  No atomics: results are bit-reproducible.
-#include "common.hpp"
+#include "f32x3_tile.hpp"
 #include "../../include/sais_hip.h"
 
 namespace {
 
-constexpr int BM = 128, BN = 128, BK = 64;
-constexpr int TILE_BYTES = BM * BK * 2;
+constexpr int BM = 128, BN = 128, BK = 64;           // the stage of f32x3_tile.hpp
 constexpr int PAD_IDX = 0x40000000;            // candidate-buffer padding: value -inf, index PAD_IDX + position
 constexpr int TARGET_WGS = 256;                // splits are added until rows x splits reaches one workgroup per CU
 constexpr int MIN_TILES_PER_SPLIT = 4, MAX_SPLITS = 64;
@@ -50,8 +49,6 @@ inline size_t knn_ws_entries(int Nq, int Nt) {
 }
 
 struct Cand { float v; int i; };
-
-DEVINL bool before(float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai < bi); }
 
 // bitonic sort of 64 R entries held as entry e = 64 r + lane, best first
 template <int R>
@@ -116,17 +113,6 @@ DEVINL float prune(Cand* buf, int cnt, int kmax, int lane) {
     return entry_value<R>(v, kmax - 1);
 }
 
-DEVINL void split8(const f32x4& a, const f32x4& b, u32x4& hi, u32x4& lo) {
-    bf16x8 h, l;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        h[i] = (bf16)a[i]; l[i] = (bf16)(a[i] - (float)h[i]);
-        h[4 + i] = (bf16)b[i]; l[4 + i] = (bf16)(b[i] - (float)h[4 + i]);
-    }
-    hi = __builtin_bit_cast(u32x4, h);
-    lo = __builtin_bit_cast(u32x4, l);
-}
-
 struct KnnSearchParams {
     const float* test;            // f32 [Nq, D]
     const float* train;           // f32 [Nt, D]                       (SPLIT == false)
@@ -140,7 +126,7 @@ DEVINL int s_off(int row, int col) { return row * 512 + ((((col >> 2) ^ (row & 3
 
 template <bool SPLIT, int R>
 __global__ __launch_bounds__(256) void knn_search_kernel(KnnSearchParams p) {
-    __shared__ __attribute__((aligned(16))) char smem[4 * TILE_BYTES];      // A_hi | A_lo | B_hi | B_lo, then the f32 tile
+    __shared__ __attribute__((aligned(16))) char smem[F32X3_LDS_BYTES];      // A_hi | A_lo | B_hi | B_lo, then the f32 tile
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int wr = wid >> 1, wc = wid & 1, g = lane >> 4, li = lane & 15;
     const int m0 = blockIdx.x * BM, split = blockIdx.y;
@@ -180,14 +166,9 @@ __global__ __launch_bounds__(256) void knn_search_kernel(KnnSearchParams p) {
     auto lstore = [&]() {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int r = sr + 32 * i;
             u32x4 hi, lo;
-            split8(ra[i][0], ra[i][1], hi, lo);
-            *(u32x4*)(smem + swz(r, sc)) = hi;
-            *(u32x4*)(smem + TILE_BYTES + swz(r, sc)) = lo;
             if constexpr (SPLIT) { hi = qh[i]; lo = ql[i]; } else split8(rb[i][0], rb[i][1], hi, lo);
-            *(u32x4*)(smem + 2 * TILE_BYTES + swz(perm_row(r), sc)) = hi;
-            *(u32x4*)(smem + 3 * TILE_BYTES + swz(perm_row(r), sc)) = lo;
+            f32x3_store_row(smem, sr + 32 * i, sc, ra[i][0], ra[i][1], hi, lo);
         }
     };
     f32x4 acc[4][4];
@@ -203,6 +184,7 @@ __global__ __launch_bounds__(256) void knn_search_kernel(KnnSearchParams p) {
         lstore();
         __syncthreads();
         if (step + 1 < nstep) gload(step + 1);
+        // own copy of f32x3_kstep (f32x3_tile.hpp): same fragments, same MFMA order
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             bf16x8 ah[4], al[4], bh[4], bl[4];
@@ -210,9 +192,9 @@ __global__ __launch_bounds__(256) void knn_search_kernel(KnnSearchParams p) {
             for (int u = 0; u < 4; ++u) {
                 const int oa = swz(wr * 64 + u * 16 + li, ks * 4 + g), ob = swz(wc * 64 + u * 16 + li, ks * 4 + g);
                 ah[u] = *(const bf16x8*)(smem + oa);
-                al[u] = *(const bf16x8*)(smem + TILE_BYTES + oa);
-                bh[u] = *(const bf16x8*)(smem + 2 * TILE_BYTES + ob);
-                bl[u] = *(const bf16x8*)(smem + 3 * TILE_BYTES + ob);
+                al[u] = *(const bf16x8*)(smem + F32X3_IMG_BYTES + oa);
+                bh[u] = *(const bf16x8*)(smem + 2 * F32X3_IMG_BYTES + ob);
+                bl[u] = *(const bf16x8*)(smem + 3 * F32X3_IMG_BYTES + ob);
             }
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt)
@@ -346,28 +328,7 @@ __global__ __launch_bounds__(64) void knn_vote_kernel(KnnVoteParams p) {
             float* o = p.votes + ((size_t)t * p.Nq + row) * C;
             for (int c = lane; c < C; c += 64) o[c] = votes[c];
         }
-        // five best classes by (vote descending, class ascending)
-        int chosen[5];
-#pragma unroll
-        for (int q = 0; q < 5; ++q) {
-            float bv = -INFINITY;
-            int bc = 0x7fffffff;
-            for (int c = lane; c < C; c += 64) {
-                bool taken = false;
-#pragma unroll
-                for (int u = 0; u < q; ++u) taken |= chosen[u] == c;
-                const float w = votes[c];
-                if (!taken && before(w, c, bv, bc)) { bv = w; bc = c; }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ov = __shfl_xor(bv, o);
-                const int oc = __shfl_xor(bc, o);
-                if (before(ov, oc, bv, bc)) { bv = ov; bc = oc; }
-            }
-            chosen[q] = bc;
-            if (lane == 0) p.pred[((size_t)t * p.Nq + row) * 5 + q] = bc == 0x7fffffff ? -1 : bc;
-        }
+        wave_best5(votes, C, lane, p.pred + ((size_t)t * p.Nq + row) * 5);      // by (vote descending, class ascending)
         __syncthreads();
     }
 }

@@ -4,48 +4,12 @@
 //             the final self.norm (:212), and norm1/norm2 of the post-norm TransformerEncoderLayer
 //             (prepare_model.py:74-81; eps 1e-5).
 //   backward: autograd of the same.
-#include "common.hpp"
+#include "row384.hpp"
 #include "philox.hpp"
 #include "../../include/sais_hip.h"
 
 namespace {
-constexpr int D = 384;
-
 struct Row12 { float v[12]; };
-
-DEVINL float half_sum(float v) {          // reduce over the 32 lanes of a half-wave
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-DEVINL int col_of(int l32, int i) { return 128 * (i >> 2) + 4 * l32 + (i & 3); }      // column of register i of lane l32
-DEVINL void load_f32(const float* p, int l32, float (&v)[12]) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        f32x4 t = *(const f32x4*)(p + 128 * i + 4 * l32);
-        v[4 * i] = t[0]; v[4 * i + 1] = t[1]; v[4 * i + 2] = t[2]; v[4 * i + 3] = t[3];
-    }
-}
-DEVINL void load_bf16(const bf16* p, int l32, float (&v)[12]) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        bf16x4 t = *(const bf16x4*)(p + 128 * i + 4 * l32);
-        v[4 * i] = (float)t[0]; v[4 * i + 1] = (float)t[1]; v[4 * i + 2] = (float)t[2]; v[4 * i + 3] = (float)t[3];
-    }
-}
-DEVINL void store_f32(float* p, int l32, const float (&v)[12]) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) *(f32x4*)(p + 128 * i + 4 * l32) = f32x4{v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]};
-}
-DEVINL void store_bf16(bf16* p, int l32, const float (&v)[12]) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        bf16x4 t;
-        t[0] = (bf16)v[4 * i]; t[1] = (bf16)v[4 * i + 1]; t[2] = (bf16)v[4 * i + 2]; t[3] = (bf16)v[4 * i + 3];
-        *(bf16x4*)(p + 128 * i + 4 * l32) = t;
-    }
-}
 
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* x, long ldx, int rows, const float* gamma,
                                                      const float* beta, float eps, bf16* y16, long ldy16,
@@ -57,7 +21,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* x, long ldx, i
     load_f32(x + (size_t)row * ldx, l32, v);
     load_f32(gamma, l32, gm);
     load_f32(beta, l32, bt);
-    float s = 0.f;
+    float s = 0.f;                            // own copy of ln_row_stats (row384.hpp)
 #pragma unroll
     for (int i = 0; i < 12; ++i) s += v[i];
     const float mu = half_sum(s) * (1.0f / D);
@@ -101,7 +65,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16* dy16, long lddy
         }
         load_f32(x + (size_t)row * ldx, l32, xv);
         const float mu = mean[row], rs = rstd[row];
-        float c1 = 0.f, c2 = 0.f;
+        float c1 = 0.f, c2 = 0.f;                    // own copy of ln_row_bwd (row384.hpp)
 #pragma unroll
         for (int i = 0; i < 12; ++i) {
             xv[i] = (xv[i] - mu) * rs;               // xhat
@@ -140,23 +104,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16* dy16, long lddy
             store_bf16(dx16 + (size_t)row * lddx16, l32, dy);
         }
     }
-    if (dgamma) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                red[0][hw][128 * i + 4 * l32 + j] = ag[4 * i + j];
-                red[1][hw][128 * i + 4 * l32 + j] = ab[4 * i + j];
-            }
-        __syncthreads();
-        for (int c = threadIdx.x; c < 2 * D; c += 256) {
-            int which = c / D, col = c - which * D;
-            float s = 0.f;
-#pragma unroll
-            for (int h = 0; h < 8; ++h) s += red[which][h][col];
-            atomicAdd((which ? dbeta : dgamma) + col, s);
-        }
-    }
+    if (dgamma) ln_flush_dgamma_dbeta(red, hw, l32, ag, ab, dgamma, dbeta);
 }
 
 // probe_features(avgpool=True) (eval_linear.py:166-170 with n = 1): one workgroup per frame normalises all its token rows;
@@ -176,14 +124,8 @@ __global__ __launch_bounds__(256) void cls_avgpool_norm_kernel(const float* x, l
     for (int row = hw; row < ntok; row += 8) {
         float v[12];
         load_f32(xf + (size_t)row * D, l32, v);
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < 12; ++i) s += v[i];
-        const float mu = half_sum(s) * (1.0f / D);
-        float q = 0.f;
-#pragma unroll
-        for (int i = 0; i < 12; ++i) { float d = v[i] - mu; q += d * d; }
-        const float rs = rsqrtf(half_sum(q) * (1.0f / D) + eps);
+        float mu, rs;
+        ln_row_stats(v, eps, mu, rs);
 #pragma unroll
         for (int i = 0; i < 12; ++i) {
             v[i] = (v[i] - mu) * rs * gm[i] + bt[i];

@@ -21,9 +21,6 @@ constexpr int BT = 64;                       // tile side of both GEMMs (rows x 
 constexpr int LK = 32, LLD = 36;             // logits: K step, LDS row stride in floats
 constexpr int UK = 32, ULD = 80;             // update: K (= batch row) step, LDS row stride in floats
 
-DEVINL f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-DEVINL bool before(float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai < bi); }
-
 struct LogitsParams {
     const float* X;      // [B, Dm]
     const float* W;      // [H, C, Dm]
@@ -114,29 +111,7 @@ __global__ __launch_bounds__(64) void probe_ce_kernel(float* Z, const int* targe
     const float lse = mx + logf(s);
     const int t = targets[row];
     if (lane == 0) loss_rows[(size_t)h * B + row] = lse - (t >= 0 && t < C ? z[t] : 0.f);      // (the host checks the range)
-    if (top5) {                                            // five best classes by (logit descending, class ascending)
-        int chosen[5];
-#pragma unroll
-        for (int q = 0; q < 5; ++q) {
-            float bv = -INFINITY;
-            int bc = 0x7fffffff;
-            for (int c = lane; c < C; c += 64) {
-                bool taken = false;
-#pragma unroll
-                for (int u = 0; u < q; ++u) taken |= chosen[u] == c;
-                const float w = z[c];
-                if (!taken && before(w, c, bv, bc)) { bv = w; bc = c; }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ov = __shfl_xor(bv, o);
-                const int oc = __shfl_xor(bc, o);
-                if (before(ov, oc, bv, bc)) { bv = ov; bc = oc; }
-            }
-            chosen[q] = bc;
-            if (lane == 0) top5[((size_t)h * B + row) * 5 + q] = bc == 0x7fffffff ? -1 : bc;
-        }
-    }
+    if (top5) wave_best5(z, C, lane, top5 + ((size_t)h * B + row) * 5);      // by (logit descending, class ascending)
     if (train) {
         const float inv = 1.0f / (float)B;
         for (int c = lane; c < C; c += 64) zr[c] = (expf(z[c] - lse) - (c == t ? 1.0f : 0.0f)) * inv;

@@ -15,14 +15,12 @@
 // 16-key tile: softmax is an in-lane loop plus two shuffles, and P^T is already the B operand of ctx^T = V^T P^T (slot g of
 // step r <-> key 4 g + r) with no lane movement.  The backward needs P and dS with the KEY on the lane as well (dV, dK sum
 // over queries): the waves re-own key tiles after a barrier and rebuild both from the per-query statistics left in LDS.
-#include "common.hpp"
+#include "attn_frag.hpp"
 #include "philox.hpp"
 #include "../../include/sais_hip.h"
 
 namespace {
 constexpr int D = 384, TH = 4, THD = 96, TLD = 100;       // TLD: floats per LDS row
-
-DEVINL f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 // row[24 g .. 24 g + 23] -> registers (times `mul`)
 DEVINL void load24(const float* row, int g, float (&f)[24], float mul = 1.0f) {
@@ -52,8 +50,6 @@ DEVINL void dot_tile2(const float (&x0)[24], const float (&y0)[24], const float 
         a1 = mfma4(x1[s], y1[s], a1);
     }
 }
-DEVINL float max4g(float v) { v = fmaxf(v, __shfl_xor(v, 16)); return fmaxf(v, __shfl_xor(v, 32)); }
-DEVINL float sum4g(float v) { v += __shfl_xor(v, 16); return v + __shfl_xor(v, 32); }
 
 // head slices q, k, v of qkv [B*S, 1152] -> sQ / sK / sV [S_pad][TLD], rows >= S zero.  Addresses are clamped instead of
 // branched on and a lane issues the loads of SU consecutive passes (3 SU float4) before the first LDS write: the
@@ -139,7 +135,7 @@ __global__ __launch_bounds__(256) void tattn_fwd_kernel(const float* qkv, const 
                 m = fmaxf(m, p[kt][r]);
             }
         }
-        m = max4g(m);
+        m = group_max(m);
         float sum = 0.f;
 #pragma unroll
         for (int kt = 0; kt < MAXT; ++kt) {
@@ -147,7 +143,7 @@ __global__ __launch_bounds__(256) void tattn_fwd_kernel(const float* qkv, const 
 #pragma unroll
             for (int r = 0; r < 4; ++r) { const float e = __expf(p[kt][r] - m); p[kt][r] = e; sum += e; }
         }
-        const float inv = 1.0f / sum4g(sum);
+        const float inv = 1.0f / group_sum(sum);
 #pragma unroll
         for (int kt = 0; kt < MAXT; ++kt) {
             if (kt >= nt) break;
@@ -259,7 +255,7 @@ __global__ __launch_bounds__(256) void tattn_bwd_kernel(const float* qkv, const 
                 m = fmaxf(m, p[kt][r]);
             }
         }
-        m = max4g(m);
+        m = group_max(m);
         float sum = 0.f;
 #pragma unroll
         for (int kt = 0; kt < MAXT; ++kt) {
@@ -267,7 +263,7 @@ __global__ __launch_bounds__(256) void tattn_bwd_kernel(const float* qkv, const 
 #pragma unroll
             for (int r = 0; r < 4; ++r) { const float e = __expf(p[kt][r] - m); p[kt][r] = e; sum += e; }
         }
-        const float inv = 1.0f / sum4g(sum);
+        const float inv = 1.0f / group_sum(sum);
         float dot = 0.f;
 #pragma unroll
         for (int kt = 0; kt < MAXT; ++kt) {
@@ -282,7 +278,7 @@ __global__ __launch_bounds__(256) void tattn_bwd_kernel(const float* qkv, const 
                 dot += pv * dp[kt][r];
             }
         }
-        dot = sum4g(dot);
+        dot = group_sum(dot);
         if (g == 0) { sM[q] = m; sI[q] = inv; sDot[q] = dot; }
 #pragma unroll
         for (int kt = 0; kt < MAXT; ++kt) {

@@ -16,12 +16,11 @@
 //   tln_bwd_kernel    the same for the backward: dy = sum_z slab_z + add, then autograd of LayerNorm, the residual-branch
 //                     dropout as a second output, dgamma / dbeta.
 // Dropout masks: Philox element index m * N + n of the site, exactly as sais_dropout_f32 / sais_dropout_mask define them.
-#include "common.hpp"
+#include "row384.hpp"
 #include "philox.hpp"
 #include "../../include/sais_hip.h"
 
 namespace {
-constexpr int D = 384;
 constexpr int TT = 64 * 128;                  // one operand half (hi or lo) of a 64 x 64 tile: 64 rows x 128 B
 
 struct TgParams {
@@ -31,17 +30,6 @@ struct TgParams {
     float* out; long ldo;
     float p_drop; const unsigned long long* rng; unsigned site;
 };
-
-DEVINL void split8(const f32x4& a, const f32x4& b, u32x4& hi, u32x4& lo) {
-    bf16x8 h, l;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        h[i] = (bf16)a[i]; l[i] = (bf16)(a[i] - (float)h[i]);
-        h[4 + i] = (bf16)b[i]; l[4 + i] = (bf16)(b[i] - (float)h[4 + i]);
-    }
-    hi = __builtin_bit_cast(u32x4, h);
-    lo = __builtin_bit_cast(u32x4, l);
-}
 
 // keep / (1 - p) factors of the four consecutive mask elements idx .. idx + 3 (idx % 4 == 0): ONE Philox block
 DEVINL f32x4 keep4(const unsigned long long* rng, unsigned site, unsigned long long idx, unsigned thr, float inv) {
@@ -168,22 +156,6 @@ __global__ __launch_bounds__(256) void tgemm_kernel(TgParams p) {
 }
 
 // ------------------------------------------------------------------------------------------------- row kernels
-DEVINL float half_sum(float v) {
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-DEVINL void ld12(const float* q, int l32, float (&v)[12]) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const f32x4 t = *(const f32x4*)(q + 128 * i + 4 * l32);
-        v[4 * i] = t[0]; v[4 * i + 1] = t[1]; v[4 * i + 2] = t[2]; v[4 * i + 3] = t[3];
-    }
-}
-DEVINL void st12(float* q, int l32, const float (&v)[12]) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) *(f32x4*)(q + 128 * i + 4 * l32) = f32x4{v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]};
-}
 // lane l32 of a half-wave owns columns 128 i + 4 l32 .. + 3 (i = 0..2) of its row: three aligned groups of four
 DEVINL void drop12(float (&v)[12], const unsigned long long* rng, unsigned site, int row, int l32, unsigned thr, float inv) {
 #pragma unroll
@@ -201,16 +173,16 @@ DEVINL void sum_slabs(const float* slabs, int nslab, long slab_stride, size_t ro
     int s = 0;
     for (; s + 4 <= nslab; s += 4) {
         float t0[12], t1[12], t2[12], t3[12];
-        ld12(slabs + (size_t)s * slab_stride + row_off, l32, t0);
-        ld12(slabs + (size_t)(s + 1) * slab_stride + row_off, l32, t1);
-        ld12(slabs + (size_t)(s + 2) * slab_stride + row_off, l32, t2);
-        ld12(slabs + (size_t)(s + 3) * slab_stride + row_off, l32, t3);
+        load_f32(slabs + (size_t)s * slab_stride + row_off, l32, t0);
+        load_f32(slabs + (size_t)(s + 1) * slab_stride + row_off, l32, t1);
+        load_f32(slabs + (size_t)(s + 2) * slab_stride + row_off, l32, t2);
+        load_f32(slabs + (size_t)(s + 3) * slab_stride + row_off, l32, t3);
 #pragma unroll
         for (int i = 0; i < 12; ++i) v[i] += (t0[i] + t1[i]) + (t2[i] + t3[i]);
     }
     for (; s < nslab; ++s) {
         float t[12];
-        ld12(slabs + (size_t)s * slab_stride + row_off, l32, t);
+        load_f32(slabs + (size_t)s * slab_stride + row_off, l32, t);
 #pragma unroll
         for (int i = 0; i < 12; ++i) v[i] += t[i];
     }
@@ -228,31 +200,25 @@ __global__ __launch_bounds__(256) void tln_fwd_kernel(const float* slabs, int ns
     float v[12], t[12];
     sum_slabs(slabs, nslab, slab_stride, (size_t)row * D, l32, v);
     if (bias) {
-        ld12(bias, l32, t);
+        load_f32(bias, l32, t);
 #pragma unroll
         for (int i = 0; i < 12; ++i) v[i] += t[i];
     }
     if (p_drop > 0.f) drop12(v, rng, site, row, l32, drop_threshold(p_drop), 1.0f / (1.0f - p_drop));
     if (resid) {
-        ld12(resid + (size_t)row * D, l32, t);
+        load_f32(resid + (size_t)row * D, l32, t);
 #pragma unroll
         for (int i = 0; i < 12; ++i) v[i] += t[i];
     }
-    if (y) st12(y + (size_t)row * D, l32, v);
+    if (y) store_f32(y + (size_t)row * D, l32, v);
     float gm[12], bt[12];
-    ld12(gamma, l32, gm);
-    ld12(beta, l32, bt);
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 12; ++i) s += v[i];
-    const float mu = half_sum(s) * (1.0f / D);
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < 12; ++i) { const float d = v[i] - mu; q += d * d; }
-    const float rs = rsqrtf(half_sum(q) * (1.0f / D) + eps);
+    load_f32(gamma, l32, gm);
+    load_f32(beta, l32, bt);
+    float mu, rs;
+    ln_row_stats(v, eps, mu, rs);
 #pragma unroll
     for (int i = 0; i < 12; ++i) v[i] = (v[i] - mu) * rs * gm[i] + bt[i];
-    st12(z + (size_t)row * D, l32, v);
+    store_f32(z + (size_t)row * D, l32, v);
     if (l32 == 0) {
         if (mean) mean[row] = mu;
         if (rstd) rstd[row] = rs;
@@ -269,56 +235,26 @@ __global__ __launch_bounds__(256) void tln_bwd_kernel(const float* slabs, int ns
     __shared__ float red[2][8][D];
     const int l32 = threadIdx.x & 31, hw = threadIdx.x >> 5;
     float gm[12], ag[12], ab[12];
-    ld12(gamma, l32, gm);
+    load_f32(gamma, l32, gm);
 #pragma unroll
     for (int i = 0; i < 12; ++i) { ag[i] = 0.f; ab[i] = 0.f; }
     for (int row = blockIdx.x * 8 + hw; row < rows; row += gridDim.x * 8) {
         float dy[12], xv[12], t[12];
         sum_slabs(slabs, nslab, slab_stride, (size_t)row * D, l32, dy);
         if (add) {
-            ld12(add + (size_t)row * D, l32, t);
+            load_f32(add + (size_t)row * D, l32, t);
 #pragma unroll
             for (int i = 0; i < 12; ++i) dy[i] += t[i];
         }
-        ld12(x + (size_t)row * D, l32, xv);
-        const float mu = mean[row], rs = rstd[row];
-        float c1 = 0.f, c2 = 0.f;
-#pragma unroll
-        for (int i = 0; i < 12; ++i) {
-            xv[i] = (xv[i] - mu) * rs;
-            ag[i] += dy[i] * xv[i];
-            ab[i] += dy[i];
-            dy[i] *= gm[i];
-            c1 += dy[i];
-            c2 += dy[i] * xv[i];
-        }
-        c1 = half_sum(c1) * (1.0f / D);
-        c2 = half_sum(c2) * (1.0f / D);
-#pragma unroll
-        for (int i = 0; i < 12; ++i) dy[i] = rs * (dy[i] - c1 - xv[i] * c2);
-        st12(dx + (size_t)row * D, l32, dy);
+        load_f32(x + (size_t)row * D, l32, xv);
+        ln_row_bwd(dy, xv, gm, mean[row], rstd[row], ag, ab);      // dy = dx
+        store_f32(dx + (size_t)row * D, l32, dy);
         if (dx_drop) {
             drop12(dy, rng, site, row, l32, drop_threshold(p_drop), 1.0f / (1.0f - p_drop));
-            st12(dx_drop + (size_t)row * D, l32, dy);
+            store_f32(dx_drop + (size_t)row * D, l32, dy);
         }
     }
-    if (dgamma) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                red[0][hw][128 * i + 4 * l32 + j] = ag[4 * i + j];
-                red[1][hw][128 * i + 4 * l32 + j] = ab[4 * i + j];
-            }
-        __syncthreads();
-        for (int c = threadIdx.x; c < 2 * D; c += 256) {
-            const int which = c / D, col = c - which * D;
-            float s = 0.f;
-#pragma unroll
-            for (int h = 0; h < 8; ++h) s += red[which][h][col];
-            atomicAdd((which ? dbeta : dgamma) + col, s);
-        }
-    }
+    if (dgamma) ln_flush_dgamma_dbeta(red, hw, l32, ag, ab, dgamma, dbeta);
 }
 }  // namespace
 

@@ -21,8 +21,6 @@ namespace {
 
 constexpr int FD = SAIS_VOS_DIM;
 
-DEVINL f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
 struct VosParams {
     const float* tar;      // [n, 384]
     const float* ctx;      // [nctx, n, 384]

@@ -6,13 +6,18 @@ LDS size, scratch size, accumulator offset).  Normalised away: comments, and the
 which counts the functions of a translation unit.
     tools/isa_diff.py <dir A> <dir B> [--json table.json --label=<build>] [--by-file]
 --by-file pairs <stem>.s with <stem>.s instead of pooling each directory.  Exit status 1 when a kernel differs, is missing on one
-side or is defined twice on one side."""
+side or is defined twice on one side.  A kernel that differs gets, in the table, what a refactor that may move registers and
+address arithmetic has to keep: "descriptors_identical" and the counts of both builds per class of tools/asm_count.py (MFMA,
+LDS, global memory) plus barriers and atomics."""
 import argparse
 import glob
 import json
 import os
 import re
 import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from asm_count import classify  # noqa: E402
 
 LABEL_FN = re.compile(r"\.L(BB|JTI|CPI|tmp|func_begin|func_end)\d+(_?)")
 
@@ -48,6 +53,19 @@ def kernels(path):
     return out
 
 
+def mix(body):
+    """{class: count} of the instruction classes that a change of register assignment or address arithmetic leaves alone."""
+    c = {"mfma": 0, "lds": 0, "vmem": 0, "barrier": 0, "atomic": 0}
+    for line in body:
+        op = line.split()[0]
+        k = classify(op)
+        if k in ("mfma", "lds", "vmem"):
+            c[k] += 1
+        c["barrier"] += op.startswith("s_barrier")
+        c["atomic"] += "_atomic_" in op
+    return c
+
+
 def pool(files):
     found, twice = {}, []
     for f in files:
@@ -68,6 +86,8 @@ def compare(a_files, b_files):
         same = k in a and k in b and a[k][0] == b[k][0] and a[k][1] == b[k][1]
         rows.append({"kernel": k, "file_a": a[k][2] if k in a else None, "file_b": b[k][2] if k in b else None,
                      "instructions_a": ia, "instructions_b": ib, "identical": same})
+        if not same and k in a and k in b:
+            rows[-1].update(descriptors_identical=a[k][1] == b[k][1], mix_a=mix(a[k][0]), mix_b=mix(b[k][0]))
     return rows, a2, b2
 
 
@@ -95,6 +115,9 @@ def main():
     for r in rows:
         if not args.quiet or not r["identical"]:
             print(f"{'same' if r['identical'] else 'DIFF':4s} {str(r['instructions_a']):>6s} {str(r['instructions_b']):>6s}  {r['kernel']}")
+            if "mix_a" in r:
+                print(f"     descriptors {'same' if r['descriptors_identical'] else 'DIFF'}, mix {'same' if r['mix_a'] == r['mix_b'] else 'DIFF'}"
+                      f"  {r['mix_a']} / {r['mix_b']}")
     for k in twice:
         print("defined twice in", k)
     print(f"{len(rows)} kernels, {sum(r['instructions_a'] or 0 for r in rows)} / {sum(r['instructions_b'] or 0 for r in rows)} instructions, "
