@@ -853,6 +853,35 @@ int sais_vos_propagate(const float* tar, const float* ctx, const float* segs, in
 int sais_vos_upsample_argmax(const float* seg, int C, int h, int w, int patch, unsigned char* labels, float* workspace,
                              void* stream);
 
+/* ================================================================ attention-map rendering
+ * (dino-main/video_generation.py and visualize_attention.py; sais_amd/csrc/attnviz.hip, host: VisionTransformer.cls_attention and
+ * sais_amd/attnviz.py).  Additive entries: the ABI version does not change.  No atomics: every entry is bit-reproducible.
+ * sais_vit_cls_probs: row 0 of the last block's softmax (Attention.forward, vision_transformer.py:83-90) at any token count.
+ *   q bf16 [frames, 384] (the CLS queries, row stride ldq), k bf16 [frames * ntok, 384] head-major (row stride ldk: the K third
+ *   of a qkv buffer is passed in place), 2 <= ntok <= SAIS_VIT_ATTN_ANY_MAX_TOKENS.  probs f32 [frames, 6, ntok] =
+ *   softmax_j(q_h . k_{j,h} / 8) over ALL ntok keys, the CLS key included; scores, row maximum and sum in fp32, keys past ntok
+ *   never enter the maximum, nothing is written past frames * 6 * ntok.  ldq, ldk multiples of 8, q and k 16-B aligned.  One
+ *   workgroup per (frame, head): a row's result does not depend on the number of frames.
+ * sais_attn_mass_mask: "keep xx% of the mass" (video_generation.py:197-205) per row.  p f32 [rows, n] (row stride ldp),
+ *   1 <= n <= SAIS_ATTN_MASK_MAX_N, 0 < threshold < 1, keep u8 [rows, n].  The row is ordered ascending by value, equal values
+ *   in ascending index order (stable); element j is kept iff its inclusive cumulative sum divided by the row sum is
+ *   > 1 - threshold.  The sums run in fp64 in one fixed order.  A row whose sum is 0 keeps nothing.
+ * sais_attn_render: p f32 [frames, nh_total, n] (row stride ldp, row = frame * nh_total + head), keep u8 [frames, nh_total, n]
+ *   or NULL (no masking), heads head0 .. head0 + nheads - 1, grid h x w with h * w == n <= SAIS_ATTN_MASK_MAX_N, 1 <= patch <= 64.
+ *   heat f32 [frames, h, w]: the sum over the heads, ascending and starting from the first term, of (p * keep) / nheads — an f32
+ *   product by 0 or 1, an f32 division, f32 additions, as numpy evaluates video_generation.py:235-238.
+ *   rgb u8 [frames, h * patch, w * patch, 3] (NULL: heat only): per frame vmin / vmax of heat, then matplotlib's Normalize and
+ *   Colormap.__call__ on f32: ((x - vmin) / (vmax - vmin)) * 256 truncated, the value 256 -> 255, index 0 everywhere for a
+ *   constant map; lut u8 [256, 3] on the device; every pixel of a patch gets the patch's colour (nearest upsampling).
+ *   workspace: SAIS_ATTN_RENDER_WS_FLOATS floats per frame, needed with rgb.  Two launches with rgb, one without.        */
+#define SAIS_ATTN_MASK_MAX_N 4096
+#define SAIS_ATTN_RENDER_WS_FLOATS 32
+int sais_vit_cls_probs(const void* q, long ldq, const void* k, long ldk, int frames, int ntok, float* probs, void* stream);
+int sais_attn_mass_mask(const float* p, long ldp, int rows, int n, double threshold, unsigned char* keep, void* stream);
+int sais_attn_render(const float* p, long ldp, const unsigned char* keep /*optional*/, int frames, int nh_total, int head0,
+                     int nheads, int h, int w, int n, int patch, const unsigned char* lut, float* heat,
+                     unsigned char* rgb /*optional*/, float* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

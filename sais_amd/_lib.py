@@ -262,6 +262,11 @@ SIGNATURES = {
     "sais_vos_propagate": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int),
                            c_void_p, c_void_p],
     "sais_vos_upsample_argmax": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    # attention-map rendering
+    "sais_vit_cls_probs": [c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p],
+    "sais_attn_mass_mask": [c_void_p, c_long, c_int, c_int, ctypes.c_double, c_void_p, c_void_p],
+    "sais_attn_render": [c_void_p, c_long, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                         c_void_p, c_void_p, c_void_p],
 }
 
 _lib = None

@@ -375,6 +375,30 @@ def vit_attn_fwd_any(qkv, frames, ntok, out, lse=None):
                           _stream()))
 
 
+def vit_cls_probs(q, k, frames, ntok, probs):
+    """Row 0 of the last block's softmax (csrc/attnviz.hip): q bf16 [frames, 384] (the CLS queries), k bf16 [frames*ntok, 384]
+    (row stride free: the K third of a qkv buffer in place) -> probs f32 [frames, 6, ntok] over all ntok keys."""
+    _chk(q, BF16, "q"); _chk(k, BF16, "k"); _chk(probs, F32, "probs")
+    _timed("vit_cls_probs", 2.0 * frames * ntok * 384, frames * ntok * (2 * 384 + 4 * 6),
+           lambda: L.call("sais_vit_cls_probs", _p(q), q.stride(0), _p(k), k.stride(0), frames, ntok, _p(probs), _stream()))
+
+
+def attn_mass_mask(p, rows, n, threshold, keep):
+    """keep u8 [rows, n]: the elements of each row of p (f32, row stride p.stride(-2)) that hold the top `threshold` share of
+    its mass (video_generation.py:197-205, stable order)."""
+    _chk(p, F32, "p"); _chk(keep, torch.uint8, "keep")
+    L.call("sais_attn_mass_mask", _p(p), p.stride(-2), rows, n, float(threshold), _p(keep), _stream())
+
+
+def attn_render(p, keep, frames, nh_total, head0, nheads, h, w, patch, lut, heat, rgb, ws):
+    """heat f32 [frames, h, w] = the mean over heads head0 .. head0 + nheads - 1 of p * keep (keep None: p); rgb u8
+    [frames, h patch, w patch, 3] (None: heat only) = matplotlib's Normalize + colormap `lut` (u8 [256, 3]) of it."""
+    _chk(p, F32, "p"); _chk(keep, torch.uint8, "keep"); _chk(lut, torch.uint8, "lut"); _chk(heat, F32, "heat")
+    _chk(rgb, torch.uint8, "rgb"); _chk(ws, F32, "workspace")
+    L.call("sais_attn_render", _p(p), p.stride(-2), _p(keep), frames, nh_total, head0, nheads, h, w, h * w, patch, _p(lut),
+           _p(heat), _p(rgb), _p(ws), _stream())
+
+
 def vit_attn_bwd(qkv, dout, out, lse, delta_ws, frames, dqkv, ntok=197):
     """out = the forward attention output (bf16 [frames*ntok, 384]) saved by vit_attn_fwd."""
     _chk(out, BF16, "out")

@@ -17,8 +17,10 @@ main_dino.py:658-663, with interpolate_pos_encoding :174-194 as a fixed bicubic 
 rates linspace(0, drop_path_rate, depth); SAIS itself only ever runs the ViT in eval(), extract_representations.py:
 279,340,362) is applied in the epilogues of the residual GEMMs as a per-row scale; the keep draws come from Philox
 (`drop_path_seed`, this library's stream, not torch's): `last_droppath_scales` holds what a forward used.
-`dense_features` alone takes other resolutions (any H x W in multiples of 16 up to 4097 tokens, inference only): its attention
-streams keys and values through LDS (csrc/attn_any.hip) instead of keeping a head resident.
+`dense_features` and `cls_attention` alone take other resolutions (any H x W in multiples of 16 up to 4097 tokens, inference
+only): their attention streams keys and values through LDS (csrc/attn_any.hip) instead of keeping a head resident, and
+`cls_attention` ends in the CLS row of the last block's softmax (csrc/attnviz.hip) instead of `get_last_selfattention`'s
+[F, 6, N, N] tensor, which stays a 224 x 224 / 96 x 96 call.
 """
 import math
 import os
@@ -306,17 +308,55 @@ class VisionTransformer(nn.Module):
         (interpolate_pos_encoding :174-194), then per block the row-generic GEMM / LayerNorm kernels around the streaming
         attention (sais_vit_attn_fwd_any).  A 224 x 224 input takes this path too (dino-main/eval_video_segmentation.py runs it
         at 480 x 832: 1561 tokens)."""
+        self._dense_check(x, "dense_features")
+        n = int(n)
+        if not 1 <= n <= self.depth:
+            raise ValueError(f"n = {n} must be in [1, {self.depth}]")
+        return self._dense_blocks(x, self.depth, n)[0]
+
+    @torch.no_grad()
+    def cls_attention(self, x):
+        """get_last_selfattention(x)[:, :, 0, :] (vision_transformer.py:216-223) at ANY resolution: x as dense_features takes it
+        (same checks, same errors), returns f32 [F, 6, 1 + hw]: the softmax row of the CLS query of the last block over all
+        tokens, the CLS key included — what video_generation.py and visualize_attention.py read.  Inference only.  Launches:
+        dense_features' for every block but the last, then the last block's norm1, the K third of its qkv GEMM over all rows,
+        the Q third over the CLS rows only and sais_vit_cls_probs: no V, no attention output, no proj, no MLP, and no
+        [F, 6, N, N] tensor.  A 224 x 224 input takes this path too.  (The full N x N probabilities off 224 x 224 are not built:
+        nothing in the reference reads them.)"""
+        Fr, ntok = self._dense_check(x, "cls_attention")
+        _, xs, xn = self._dense_blocks(x, self.depth - 1, 0)
+        f, dev, M = self.flat, x.device, Fr * ntok
+        p = f"blocks.{self.depth - 1}."
+        if self.depth == 1 or M < ops.ROW_GEMM_MIN_M:     # otherwise the previous block's fc2 wrote this norm1 in its epilogue
+            ops.layernorm_fwd(xs, M, D, f.w32(p + "norm1.weight"), f.w32(p + "norm1.bias"), 1e-6, y16=xn)
+        Wq, bq = f.w(p + "attn.qkv.weight"), f.w32(p + "attn.qkv.bias")
+        k = torch.empty(M, D, dtype=torch.bfloat16, device=dev)
+        q = torch.empty(Fr, D, dtype=torch.bfloat16, device=dev)
+        ops.gemm_nt(xn, Wq[D:2 * D], L.EPI_BIAS_BF16, k, bias=bq[D:2 * D])
+        ops.gemm_nt(xn.view(Fr, ntok, D)[:, 0], Wq[:D], L.EPI_BIAS_BF16, q, bias=bq[:D])
+        probs = torch.empty(Fr, HEADS, ntok, dtype=torch.float32, device=dev)
+        ops.vit_cls_probs(q, k, Fr, ntok, probs)
+        return probs
+
+    @staticmethod
+    def _dense_check(x, who):
+        """The input checks of dense_features / cls_attention -> (frames, tokens)."""
         if not isinstance(x, torch.Tensor) or not x.is_cuda:
-            raise L.SaisHipError("VisionTransformer.dense_features needs a device tensor: the HIP path has no CPU fallback")
+            raise L.SaisHipError(f"VisionTransformer.{who} needs a device tensor: the HIP path has no CPU fallback")
         if x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1 or x.shape[2] < 16 or x.shape[3] < 16 or x.shape[2] % 16 or x.shape[3] % 16:
             raise ValueError(f"expected [F,3,H,W] with H and W positive multiples of 16, got {tuple(x.shape)}")
         Fr, H, W = x.shape[0], x.shape[2], x.shape[3]
         ntok = 1 + (H // 16) * (W // 16)
         if ntok > MAX_DENSE_TOKENS:
             raise ValueError(f"{H} x {W} frames are {ntok} tokens; at most {MAX_DENSE_TOKENS}")
-        n = int(n)
-        if not 1 <= n <= self.depth:
-            raise ValueError(f"n = {n} must be in [1, {self.depth}]")
+        return Fr, ntok
+
+    def _dense_blocks(self, x, nblocks, n):
+        """The any-resolution launch list: embedding, then blocks 0 .. nblocks - 1 (every row of each).  Returns (norm(x) after each
+        of the last n blocks of the model, the residual stream f32 [M, 384], the bf16 norm1 buffer — which holds the NEXT block's
+        norm1 when nblocks < depth and the fused epilogue ran)."""
+        Fr, H, W = x.shape[0], x.shape[2], x.shape[3]
+        ntok = 1 + (H // 16) * (W // 16)
         x = x.contiguous().float()
         f, dev = self._engine(x.device), x.device
         M = Fr * ntok
@@ -330,7 +370,7 @@ class VisionTransformer(nn.Module):
         fused = M >= ops.ROW_GEMM_MIN_M               # LayerNorm in the epilogue of the N = 384 GEMMs, as _forward_kernels
         xn, qkv, ao, xn2, h = e16(M, D), e16(M, 3 * D), e16(M, D), e16(M, D), e16(M, HID)
         out = []
-        for i in range(self.depth):
+        for i in range(nblocks):
             p, last = f"blocks.{i}.", i == self.depth - 1
             if i == 0 or not fused:
                 ops.layernorm_fwd(xs, M, D, f.w32(p + "norm1.weight"), f.w32(p + "norm1.bias"), 1e-6, y16=xn)
@@ -353,7 +393,7 @@ class VisionTransformer(nn.Module):
                 y = e32(Fr, ntok, D)
                 ops.layernorm_fwd(xs, M, D, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6, y32=y)
                 out.append(y)
-        return out
+        return out, xs, xn
 
     def _dense_pos_table(self, H, W, dev):
         """The positional table f32 [1 + (H/16)(W/16), 384] of H x W frames; the bicubic map is cached per (H, W)."""
