@@ -30,17 +30,8 @@ from pathlib import Path
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", ".."))
-from sais_amd import knn, linear  # noqa: E402
-from sais_amd.vit import vit_small  # noqa: E402
-
-
-def bool_flag(s):
-    """utils.bool_flag (utils.py:201-212)."""
-    if s.lower() in {"off", "false", "0"}:
-        return False
-    if s.lower() in {"on", "true", "1"}:
-        return True
-    raise argparse.ArgumentTypeError("invalid value for a boolean flag")
+from sais_amd import linear  # noqa: E402
+from sais_amd.model_io import bool_flag, load_dino_backbone  # noqa: E402
 
 
 def get_args_parser():
@@ -78,20 +69,9 @@ EXTRA_FLAGS = ("linear_weights", "seed")
 
 
 def build_model(args, dev):
-    if args.arch.replace("deit", "vit") != "vit_small" or args.patch_size != 16:
-        raise NotImplementedError("MI355X path: --arch vit_small --patch_size 16")
-    model = vit_small(patch_size=16, num_classes=0).to(dev)
-    if args.pretrained_weights and os.path.isfile(args.pretrained_weights):
-        ckpt = torch.load(args.pretrained_weights, map_location="cpu", weights_only=False)
-        if args.checkpoint_key is not None and isinstance(ckpt, dict) and args.checkpoint_key in ckpt:
-            print(f"Take key {args.checkpoint_key} in provided checkpoint dict")
-        msg = model.load_state_dict(knn.backbone_state_dict(ckpt, args.checkpoint_key), strict=False)
-        print('Pretrained weights found at {} and loaded with msg: {}'.format(args.pretrained_weights, msg))
-    else:
-        print("Please use the `--pretrained_weights` argument to indicate the path of the checkpoint to evaluate.")
-        print("There is no reference to load pretrained weights from: the model keeps its random weights.")
+    model = load_dino_backbone(args, dev)
     print(f"Model {args.arch} built.")
-    return model.eval()
+    return model
 
 
 def lr_tag(v):

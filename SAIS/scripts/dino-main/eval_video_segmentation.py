@@ -20,7 +20,7 @@ Decisions where this script differs from the reference:
     std of 0.228 for red included (:244).  Pillow's filter is not cv2.resize's: this step is PARITY-UNPINNED.
   * --bs.  The reference parses it and ignores it.  Features do not depend on the propagation, so this script extracts the
     dense features of --bs frames per ViT pass and then propagates frame by frame.
-  * Checkpoints.  Loaded as eval_knn.py does (sais_amd.knn.backbone_state_dict); without --pretrained_weights the weights stay
+  * Checkpoints.  Loaded as eval_knn.py does (sais_amd.model_io.load_dino_backbone); without --pretrained_weights the weights stay
     random (seeded: the same in every run) and the script says so (no download).  Only --arch vit_small --patch_size 16.
 """
 import argparse
@@ -31,8 +31,8 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", ".."))
-from sais_amd import knn, vos  # noqa: E402
-from sais_amd.vit import vit_small  # noqa: E402
+from sais_amd import vos  # noqa: E402
+from sais_amd.model_io import load_dino_backbone  # noqa: E402
 
 
 def get_args_parser():
@@ -52,22 +52,8 @@ def get_args_parser():
 
 
 def build_model(args, dev):
-    if args.arch.replace("deit", "vit") != "vit_small" or args.patch_size != 16:
-        raise NotImplementedError("MI355X path: --arch vit_small --patch_size 16")
-    model = vit_small(patch_size=16, num_classes=0).to(dev)
     print(f"Model {args.arch} {args.patch_size}x{args.patch_size} built.")
-    if args.pretrained_weights and os.path.isfile(args.pretrained_weights):
-        ckpt = torch.load(args.pretrained_weights, map_location="cpu", weights_only=False)
-        if args.checkpoint_key is not None and isinstance(ckpt, dict) and args.checkpoint_key in ckpt:
-            print(f"Take key {args.checkpoint_key} in provided checkpoint dict")
-        msg = model.load_state_dict(knn.backbone_state_dict(ckpt, args.checkpoint_key), strict=False)
-        print('Pretrained weights found at {} and loaded with msg: {}'.format(args.pretrained_weights, msg))
-    else:
-        print("Please use the `--pretrained_weights` argument to indicate the path of the checkpoint to evaluate.")
-        print("There is no reference to load pretrained weights from: the model keeps its random weights.")
-    for p in model.parameters():
-        p.requires_grad = False
-    return model.eval()
+    return load_dino_backbone(args, dev, seed=0, freeze=True)
 
 
 @torch.no_grad()
@@ -106,7 +92,6 @@ def main(argv=None):
     args = get_args_parser().parse_args(argv)
     print("\n".join("%s: %s" % (k, str(v)) for k, v in sorted(dict(vars(args)).items())))
     dev = torch.device("cuda:0")
-    torch.manual_seed(0)                          # (a backbone without --pretrained_weights is the same in every invocation)
     model = build_model(args, dev)
     video_list = open(os.path.join(args.data_path, "ImageSets/2017/val.txt")).readlines()
     for i, video_name in enumerate(video_list):

@@ -27,15 +27,7 @@ import torch.distributed as dist
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", ".."))
 from sais_amd import dino  # noqa: E402
 from sais_amd.dino_data import DataAugmentationDINO, SurgDataset, collate_raw, gpu_crops  # noqa: E402
-
-
-def bool_flag(s):
-    """utils.bool_flag (utils.py:201-212)."""
-    if s.lower() in {"off", "false", "0"}:
-        return False
-    if s.lower() in {"on", "true", "1"}:
-        return True
-    raise argparse.ArgumentTypeError("invalid value for a boolean flag")
+from sais_amd.model_io import bool_flag  # noqa: E402
 
 
 FLAGS = [  # (flag, type, default)   — the reference parser, main_dino.py:48-141

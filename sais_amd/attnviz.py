@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .model_io import load_dino_backbone
 
 MAX_N, RENDER_WS_FLOATS = 4096, 32                  # SAIS_ATTN_MASK_MAX_N, SAIS_ATTN_RENDER_WS_FLOATS
 MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)      # video_generation.py:163-165, visualize_attention.py:168
@@ -209,24 +210,5 @@ def load_frame(path, resize=None, patch=16):
 
 
 def build_model(args, dev):
-    """The backbone of the two scripts: vit_small / 16 with --pretrained_weights loaded as eval_knn.py does, else random (seeded)
-    weights and a message; never a download."""
-    import os
-    from . import knn
-    from .vit import vit_small
-    if args.arch.replace("deit", "vit") != "vit_small" or args.patch_size != 16:
-        raise NotImplementedError("MI355X path: --arch vit_small --patch_size 16")
-    torch.manual_seed(0)                          # (a backbone without --pretrained_weights is the same in every invocation)
-    model = vit_small(patch_size=16, num_classes=0).to(dev)
-    if args.pretrained_weights and os.path.isfile(args.pretrained_weights):
-        ckpt = torch.load(args.pretrained_weights, map_location="cpu", weights_only=False)
-        if args.checkpoint_key is not None and isinstance(ckpt, dict) and args.checkpoint_key in ckpt:
-            print(f"Take key {args.checkpoint_key} in provided checkpoint dict")
-        msg = model.load_state_dict(knn.backbone_state_dict(ckpt, args.checkpoint_key), strict=False)
-        print('Pretrained weights found at {} and loaded with msg: {}'.format(args.pretrained_weights, msg))
-    else:
-        print("Please use the `--pretrained_weights` argument to indicate the path of the checkpoint to evaluate.")
-        print("There is no reference to load pretrained weights from: the model keeps its random (seeded) weights.")
-    for p in model.parameters():
-        p.requires_grad = False
-    return model.eval()
+    """The backbone of the two scripts: frozen, and seeded so that it is the same in every run without --pretrained_weights."""
+    return load_dino_backbone(args, dev, seed=0, freeze=True, random="random (seeded)")

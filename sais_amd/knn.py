@@ -13,6 +13,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .model_io import backbone_state_dict  # noqa: F401  (its home; the name stays importable from here)
 
 MAX_K, MAX_DIM, MAX_CLASSES, MAX_KS = 256, 1536, 4096, 8
 IMG_EXTENSIONS = (".jpg", ".jpeg", ".png", ".ppm", ".bmp", ".pgm", ".tif", ".tiff", ".webp")     # torchvision's ImageFolder
@@ -165,16 +166,6 @@ class EvalImageFolder(torch.utils.data.Dataset):
         from PIL import Image
         with open(self.samples[i][0], "rb") as fh:
             return self.transform(Image.open(fh)), i
-
-
-def backbone_state_dict(ckpt, checkpoint_key="teacher"):
-    """utils.load_pretrained_weights (utils.py:55-65): take `checkpoint_key` when the file has it, strip the `module.` and
-    `backbone.` prefixes.  A bare backbone state_dict passes through."""
-    sd = ckpt
-    if checkpoint_key is not None and isinstance(ckpt, dict) and checkpoint_key in ckpt:
-        sd = ckpt[checkpoint_key]
-    sd = {k.replace("module.", ""): v for k, v in sd.items()}
-    return {k.replace("backbone.", ""): v for k, v in sd.items()}
 
 
 @torch.no_grad()

@@ -6,7 +6,10 @@ and the save step of `trainModel` (train.py:98-121).  File contracts (SURVEY App
   prototypes.zip  torch.save(nn.ParameterDict{'0': Parameter[1,256], ...})  — a pickled module object,
                   so torch >= 2.6 needs weights_only=False
   dino_deitsmall16_pretrain.pth   plain state_dict of vit_small, 150 tensors, loaded strict
+  checkpoint.pth  of main_dino.py: {'student': ..., 'teacher': ..., ...} with `module.` / `backbone.` prefixes — the frozen
+                  backbone of the DINO tools (eval_knn.py, eval_linear.py, eval_video_segmentation.py, the attention-map scripts)
 """
+import argparse
 import os
 
 import torch
@@ -92,3 +95,48 @@ def load_vit(path=None, device='cuda:0', drop_path_rate=0.1):
             sd = {'.'.join(k.split('.')[2:]): v for k, v in items}
         model.load_state_dict(sd, strict=True)
     return model.to(device).eval()
+
+
+def backbone_state_dict(ckpt, checkpoint_key="teacher"):
+    """utils.load_pretrained_weights (utils.py:55-65): take `checkpoint_key` when the file has it, strip the `module.` and
+    `backbone.` prefixes.  A bare backbone state_dict passes through."""
+    sd = ckpt
+    if checkpoint_key is not None and isinstance(ckpt, dict) and checkpoint_key in ckpt:
+        sd = ckpt[checkpoint_key]
+    sd = {k.replace("module.", ""): v for k, v in sd.items()}
+    return {k.replace("backbone.", ""): v for k, v in sd.items()}
+
+
+def load_dino_backbone(args, dev, seed=None, freeze=False, random="random"):
+    """The frozen backbone of a DINO tool from its parsed flags (--arch, --patch_size, --pretrained_weights,
+    --checkpoint_key): vit_small / 16 in eval(), with the checkpoint loaded as utils.load_pretrained_weights does, else the
+    weights of its initialisation and a message; never a download.  seed: torch's seed before the initialisation (a backbone
+    without --pretrained_weights is then the same in every invocation); freeze: no parameter requires a gradient; random:
+    how the message names the weights that stay."""
+    if args.arch.replace("deit", "vit") != "vit_small" or args.patch_size != 16:
+        raise NotImplementedError("MI355X path: --arch vit_small --patch_size 16")
+    if seed is not None:
+        torch.manual_seed(seed)
+    model = vit_small(patch_size=16, num_classes=0).to(dev)
+    if args.pretrained_weights and os.path.isfile(args.pretrained_weights):
+        ckpt = torch.load(args.pretrained_weights, map_location="cpu", weights_only=False)
+        if args.checkpoint_key is not None and isinstance(ckpt, dict) and args.checkpoint_key in ckpt:
+            print(f"Take key {args.checkpoint_key} in provided checkpoint dict")
+        msg = model.load_state_dict(backbone_state_dict(ckpt, args.checkpoint_key), strict=False)
+        print('Pretrained weights found at {} and loaded with msg: {}'.format(args.pretrained_weights, msg))
+    else:
+        print("Please use the `--pretrained_weights` argument to indicate the path of the checkpoint to evaluate.")
+        print(f"There is no reference to load pretrained weights from: the model keeps its {random} weights.")
+    if freeze:
+        for p in model.parameters():
+            p.requires_grad = False
+    return model.eval()
+
+
+def bool_flag(s):
+    """utils.bool_flag (utils.py:201-212), the argparse type of the DINO tools' on / off flags."""
+    if s.lower() in {"off", "false", "0"}:
+        return False
+    if s.lower() in {"on", "true", "1"}:
+        return True
+    raise argparse.ArgumentTypeError("invalid value for a boolean flag")

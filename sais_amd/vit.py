@@ -36,7 +36,7 @@ from .flat import ensure_flat
 
 D, NTOK, HEADS, HID, PATCH_K = 384, 197, 6, 1536, 768
 _PRUNE_Q = os.environ.get("SAIS_VIT_PRUNE_Q", "1") != "0"     # the CLS-only last block computes q for the CLS rows only
-SIDES = {224: 197, 96: 37}          # supported frame sizes -> tokens (the attention kernels are instantiated per count)
+SIDES = {224: 197, 96: 37}          # frame sizes forward() takes -> tokens (the resident attention is instantiated per count)
 MAX_DENSE_TOKENS = 4097             # dense_features: the streaming attention (sais_vit_attn_fwd_any) takes any count up to this
 
 
@@ -116,12 +116,18 @@ def _row_groups(imgs):
     ranges as slices (`rows`, `prows`, `frames`), the interpolation map (set by the embedding).  Returns also the three totals."""
     groups, off, poff, foff = [], 0, 0, 0
     for im in imgs:
-        Fr, ntok = im.shape[0], SIDES[im.shape[-1]]
+        Fr, ntok = im.shape[0], 1 + (im.shape[2] // 16) * (im.shape[3] // 16)
         n, npat = Fr * ntok, Fr * (ntok - 1)
         groups.append(dict(Fr=Fr, ntok=ntok, off=off, poff=poff, foff=foff, interp=None, rows=slice(off, off + n),
                            prows=slice(poff, poff + npat), frames=slice(foff, foff + Fr)))
         off, poff, foff = off + n, poff + npat, foff + Fr
     return groups, off, poff, foff
+
+
+def _rows(t, g):
+    """Group g's rows of a stacked [M, ...] tensor: the tensor itself when g is the only group (a view costs the host a few
+    microseconds, twice per block in passes that are bound by the launch rate)."""
+    return t if t.shape[0] == g["Fr"] * g["ntok"] else t[g["rows"]]
 
 
 class _PendingDW:
@@ -200,7 +206,7 @@ class VisionTransformer(nn.Module):
                 nn.init.constant_(m.weight, 1.0)
         self.flat = None
         self._anchor = None
-        self._interp = {}                            # frame side, or (H, W) of dense_features -> device f32 [ntok - 1, 196] bicubic map
+        self._interp = {}                            # (H, W) -> device f32 [ntok - 1, 196] bicubic map
         self.grad_ready_hook = None                  # callable(lo, hi): flat-grad slice [lo,hi) is final
         self._t_names = [f"blocks.{i}.{n}.weight" for i in range(depth) for n in ("attn.qkv", "attn.proj", "mlp.fc1", "mlp.fc2")]
 
@@ -241,7 +247,23 @@ class VisionTransformer(nn.Module):
     def get_last_selfattention(self, x):
         x = self._check_input(x)
         self._engine(x.device)
-        return self._forward_kernels(x, save=False, want_last_attn=True)[0]
+        return self._forward_kernels(x, save=False, end="probs")[0]
+
+    def _last_norms(self, x, n, streaming):
+        """norm(x) after each of the last n blocks, oldest first, as n tensors f32 [F, ntok, 384]: every row of every block, and
+        the residual stream is updated in place, so each is normalised before the next block runs."""
+        n = int(n)
+        if not 1 <= n <= self.depth:
+            raise ValueError(f"n = {n} must be in [1, {self.depth}]")
+        f, Fr, out = self._engine(x.device), x.shape[0], []
+
+        def tap(i, xs):
+            if i >= self.depth - n:
+                y = torch.empty(Fr, xs.shape[0] // Fr, D, dtype=torch.float32, device=x.device)
+                ops.layernorm_fwd(xs, xs.shape[0], D, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6, y32=y)
+                out.append(y)
+        self._forward_kernels(x, save=False, end="blocks", tap=tap, streaming=streaming)
+        return out
 
     @torch.no_grad()
     def get_intermediate_layers(self, x, n=1):
@@ -251,18 +273,7 @@ class VisionTransformer(nn.Module):
         x = self._check_input(x)
         if x.shape[-1] != 224:
             raise ValueError("get_intermediate_layers takes 224 x 224 frames")
-        n = int(n)
-        if not 1 <= n <= self.depth:
-            raise ValueError(f"n = {n} must be in [1, {self.depth}]")
-        f, Fr, out = self._engine(x.device), x.shape[0], []
-
-        def tap(i, xs):            # the residual stream is updated in place: normalise it before the next block runs
-            if i >= self.depth - n:
-                y = torch.empty(Fr, NTOK, D, dtype=torch.float32, device=x.device)
-                ops.layernorm_fwd(xs, Fr * NTOK, D, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6, y32=y)
-                out.append(y)
-        self._forward_kernels(x, save=False, tap=tap, prune=False)
-        return out
+        return self._last_norms(x, n, streaming=False)
 
     @torch.no_grad()
     def probe_features(self, x, n=4, avgpool=False):
@@ -282,10 +293,9 @@ class VisionTransformer(nn.Module):
             raise ValueError(f"n = {n} must be in [1, {self.depth}]")
         f, Fr = self._engine(x.device), x.shape[0]
         if avgpool:
-            last = []
-            self._forward_kernels(x, save=False, tap=lambda i, xs: last.append(xs) if i == self.depth - 1 else None, prune=False)
+            xs = self._forward_kernels(x, save=False, end="blocks")[0]
             feats = torch.empty(Fr, 2 * D, dtype=torch.float32, device=x.device)
-            ops.vit_cls_avgpool_norm(last[0], Fr, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6, feats)
+            ops.vit_cls_avgpool_norm(xs, Fr, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6, feats)
             return feats
         if n == 1:
             return self._forward_kernels(x, save=False)[0]
@@ -303,16 +313,12 @@ class VisionTransformer(nn.Module):
     def dense_features(self, x, n=1):
         """get_intermediate_layers (vision_transformer.py:225-233) at ANY resolution: x f32 [F, 3, H, W] on the device, H and W
         multiples of 16 (not necessarily equal), 1 + (H/16)(W/16) <= 4097 tokens.  Returns n tensors f32 [F, 1 + hw, 384],
-        oldest first: norm(x) after each of the last n blocks.  Inference only, every row of every block is computed.  Its own
-        launch list: patchify_rect, the patch GEMM with the positional table interpolated to (H, W)
-        (interpolate_pos_encoding :174-194), then per block the row-generic GEMM / LayerNorm kernels around the streaming
-        attention (sais_vit_attn_fwd_any).  A 224 x 224 input takes this path too (dino-main/eval_video_segmentation.py runs it
-        at 480 x 832: 1561 tokens)."""
-        self._dense_check(x, "dense_features")
-        n = int(n)
-        if not 1 <= n <= self.depth:
-            raise ValueError(f"n = {n} must be in [1, {self.depth}]")
-        return self._dense_blocks(x, self.depth, n)[0]
+        oldest first: norm(x) after each of the last n blocks.  Inference only, every row of every block is computed.  The
+        launch list of forward() (_forward_kernels) with `streaming`: patchify_rect, the patch GEMM with the positional table
+        interpolated to (H, W) (interpolate_pos_encoding :174-194), then per block the row-generic GEMM / LayerNorm kernels
+        around the streaming attention (sais_vit_attn_fwd_any).  A 224 x 224 input takes these kernels too
+        (dino-main/eval_video_segmentation.py runs it at 480 x 832: 1561 tokens)."""
+        return self._last_norms(self._check_input(x, "dense_features"), n, streaming=True)
 
     @torch.no_grad()
     def cls_attention(self, x):
@@ -323,12 +329,11 @@ class VisionTransformer(nn.Module):
         the Q third over the CLS rows only and sais_vit_cls_probs: no V, no attention output, no proj, no MLP, and no
         [F, 6, N, N] tensor.  A 224 x 224 input takes this path too.  (The full N x N probabilities off 224 x 224 are not built:
         nothing in the reference reads them.)"""
-        Fr, ntok = self._dense_check(x, "cls_attention")
-        _, xs, xn = self._dense_blocks(x, self.depth - 1, 0)
-        f, dev, M = self.flat, x.device, Fr * ntok
+        x = self._check_input(x, "cls_attention")
+        f, dev, Fr = self._engine(x.device), x.device, x.shape[0]
+        xn = self._forward_kernels(x, save=False, end="norm1", streaming=True)[0]
+        M, ntok = xn.shape[0], xn.shape[0] // Fr
         p = f"blocks.{self.depth - 1}."
-        if self.depth == 1 or M < ops.ROW_GEMM_MIN_M:     # otherwise the previous block's fc2 wrote this norm1 in its epilogue
-            ops.layernorm_fwd(xs, M, D, f.w32(p + "norm1.weight"), f.w32(p + "norm1.bias"), 1e-6, y16=xn)
         Wq, bq = f.w(p + "attn.qkv.weight"), f.w32(p + "attn.qkv.bias")
         k = torch.empty(M, D, dtype=torch.bfloat16, device=dev)
         q = torch.empty(Fr, D, dtype=torch.bfloat16, device=dev)
@@ -339,113 +344,61 @@ class VisionTransformer(nn.Module):
         return probs
 
     @staticmethod
-    def _dense_check(x, who):
-        """The input checks of dense_features / cls_attention -> (frames, tokens)."""
+    def _check_input(x, any_size=None):
+        """forward()'s input as a contiguous f32 tensor.  any_size: the name of the caller that takes every H x W in multiples of
+        16 (dense_features, cls_attention) instead of the square sides of SIDES."""
+        if any_size is None:
+            if not x.is_cuda:
+                raise L.SaisHipError("VisionTransformer.forward needs a device tensor: the HIP path has no CPU fallback")
+            if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3] or x.shape[2] not in SIDES:
+                raise ValueError(f"expected [F,3,S,S] with S in {sorted(SIDES)}, got {tuple(x.shape)}")
+            return x.contiguous().float()
         if not isinstance(x, torch.Tensor) or not x.is_cuda:
-            raise L.SaisHipError(f"VisionTransformer.{who} needs a device tensor: the HIP path has no CPU fallback")
+            raise L.SaisHipError(f"VisionTransformer.{any_size} needs a device tensor: the HIP path has no CPU fallback")
         if x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1 or x.shape[2] < 16 or x.shape[3] < 16 or x.shape[2] % 16 or x.shape[3] % 16:
             raise ValueError(f"expected [F,3,H,W] with H and W positive multiples of 16, got {tuple(x.shape)}")
-        Fr, H, W = x.shape[0], x.shape[2], x.shape[3]
+        H, W = x.shape[2], x.shape[3]
         ntok = 1 + (H // 16) * (W // 16)
         if ntok > MAX_DENSE_TOKENS:
             raise ValueError(f"{H} x {W} frames are {ntok} tokens; at most {MAX_DENSE_TOKENS}")
-        return Fr, ntok
+        return x.contiguous().float()
 
-    def _dense_blocks(self, x, nblocks, n):
-        """The any-resolution launch list: embedding, then blocks 0 .. nblocks - 1 (every row of each).  Returns (norm(x) after each
-        of the last n blocks of the model, the residual stream f32 [M, 384], the bf16 norm1 buffer — which holds the NEXT block's
-        norm1 when nblocks < depth and the fused epilogue ran)."""
-        Fr, H, W = x.shape[0], x.shape[2], x.shape[3]
-        ntok = 1 + (H // 16) * (W // 16)
-        x = x.contiguous().float()
-        f, dev = self._engine(x.device), x.device
-        M = Fr * ntok
-        e16, e32 = _empty(torch.bfloat16, dev), _empty(torch.float32, dev)
-        patches, xs = e16(Fr * (ntok - 1), PATCH_K), e32(M, D)
-        ops.patchify_rect(x, patches)
-        pos = self._dense_pos_table(H, W, dev)
-        ops.gemm_nt(patches, f.w("patch_embed.proj.weight").view(D, PATCH_K), L.EPI_PATCH_F32, xs.view(Fr, ntok, D),
-                    bias=f.w32("patch_embed.proj.bias"), aux=pos, grp=(ntok - 1, ntok, 1))
-        ops.vit_cls_rows(f.w32("cls_token"), pos, xs.view(Fr, ntok, D), Fr, ntok)
-        fused = M >= ops.ROW_GEMM_MIN_M               # LayerNorm in the epilogue of the N = 384 GEMMs, as _forward_kernels
-        xn, qkv, ao, xn2, h = e16(M, D), e16(M, 3 * D), e16(M, D), e16(M, D), e16(M, HID)
-        out = []
-        for i in range(nblocks):
-            p, last = f"blocks.{i}.", i == self.depth - 1
-            if i == 0 or not fused:
-                ops.layernorm_fwd(xs, M, D, f.w32(p + "norm1.weight"), f.w32(p + "norm1.bias"), 1e-6, y16=xn)
-            ops.gemm_nt(xn, f.w(p + "attn.qkv.weight"), L.EPI_BIAS_BF16, qkv, bias=f.w32(p + "attn.qkv.bias"))
-            ops.vit_attn_fwd_any(qkv, Fr, ntok, ao)
-            if fused:
-                ops.gemm_ln_fwd(ao, f.w(p + "attn.proj.weight"), f.w32(p + "attn.proj.bias"), xs, xs, xn2,
-                                f.w32(p + "norm2.weight"), f.w32(p + "norm2.bias"), 1e-6)
-            else:
-                ops.gemm_nt(ao, f.w(p + "attn.proj.weight"), L.EPI_BIAS_RESID_F32, xs, bias=f.w32(p + "attn.proj.bias"), aux=xs)
-                ops.layernorm_fwd(xs, M, D, f.w32(p + "norm2.weight"), f.w32(p + "norm2.bias"), 1e-6, y16=xn2)
-            ops.gemm_nt(xn2, f.w(p + "mlp.fc1.weight"), L.EPI_BIAS_GELU_BF16, h, bias=f.w32(p + "mlp.fc1.bias"))
-            if fused and not last:
-                q = f"blocks.{i + 1}."
-                ops.gemm_ln_fwd(h, f.w(p + "mlp.fc2.weight"), f.w32(p + "mlp.fc2.bias"), xs, xs, xn,
-                                f.w32(q + "norm1.weight"), f.w32(q + "norm1.bias"), 1e-6)
-            else:
-                ops.gemm_nt(h, f.w(p + "mlp.fc2.weight"), L.EPI_BIAS_RESID_F32, xs, bias=f.w32(p + "mlp.fc2.bias"), aux=xs)
-            if i >= self.depth - n:                   # the stream is updated in place: normalise it before the next block
-                y = e32(Fr, ntok, D)
-                ops.layernorm_fwd(xs, M, D, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6, y32=y)
-                out.append(y)
-        return out, xs, xn
-
-    def _dense_pos_table(self, H, W, dev):
-        """The positional table f32 [1 + (H/16)(W/16), 384] of H x W frames; the bicubic map is cached per (H, W)."""
+    def _pos_table(self, H, W, dev):
+        """(positional table f32 [1 + (H/16)(W/16), 384], interpolation map or None) for H x W frames; the bicubic map is cached
+        per (H, W)."""
         pos = self.flat.w32("pos_embed").view(NTOK, D)
         if H == W == 224:
-            return pos
+            return pos, None
         Wm = self._interp.get((H, W))
         if Wm is None or Wm.device != dev:
             Wm = torch.from_numpy(pos_interp_matrix(14, H, W).astype(np.float32)).to(dev)
             self._interp[(H, W)] = Wm
         out = torch.empty(1 + Wm.shape[0], D, dtype=torch.float32, device=dev)
         ops.pos_interp_fwd(Wm, pos, out)
-        return out
-
-    def _check_input(self, x):
-        if not x.is_cuda:
-            raise L.SaisHipError("VisionTransformer.forward needs a device tensor: the HIP path has no CPU fallback")
-        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3] or x.shape[2] not in SIDES:
-            raise ValueError(f"expected [F,3,S,S] with S in {sorted(SIDES)}, got {tuple(x.shape)}")
-        return x.contiguous().float()
-
-    def _pos_table(self, side, dev):
-        """(positional table f32 [ntok, 384], interpolation map or None) for frames of this side."""
-        pos = self.flat.w32("pos_embed").view(NTOK, D)
-        if side == 224:
-            return pos, None
-        Wm = self._interp.get(side)
-        if Wm is None or Wm.device != dev:
-            Wm = torch.from_numpy(pos_interp_matrix(14, side, side).astype(np.float32)).to(dev)
-            self._interp[side] = Wm
-        out = torch.empty(SIDES[side], D, dtype=torch.float32, device=dev)
-        ops.pos_interp_fwd(Wm, pos, out)
         return out, Wm
 
     # ------------------------------------------------------------------ forward kernels
-    def _forward_kernels(self, img, save, want_last_attn=False, tap=None, prune=True, reps_out=None):
-        """img: one [F,3,S,S] tensor, or a LIST of them with different S (DINO's multi-crop student, utils.py:611-630):
+    def _forward_kernels(self, img, save, end="reps", tap=None, reps_out=None, streaming=False):
+        """img: one [F,3,H,W] tensor, or a LIST of them with different sizes (DINO's multi-crop student, utils.py:611-630):
         the groups are then stacked along the token-row axis and every GEMM / LayerNorm of a block runs ONCE over all rows
         (only attention, the embedding glue and the final CLS gather are per group) — 44 160 rows in one launch fill the
-        chip where 25 216 + 18 944 in two launches leave workgroup slots empty.  Returns reps f32 [sum F, 384] in group
-        order.  tap(i, x): called after every block but a CLS-only last one with the residual stream the block left (without
-        `save` the next block overwrites it); prune = False: the last block computes every row; reps_out: a [sum F, 384] view
-        (any row stride) that receives reps instead of a new tensor."""
+        chip where 25 216 + 18 944 in two launches leave workgroup slots empty.  Returns (result, saved).  `end` names where
+        the pass stops and what the result is: "reps": after the final norm, reps f32 [sum F, 384] in group order; "probs":
+        in the last block's attention, its probabilities (get_last_selfattention); "norm1": at the last block's norm1, its bf16
+        output [M, 384] (cls_attention); "blocks": after the last block, the residual stream f32 [M, 384], every row computed
+        and no final norm.  streaming: any H x W in multiples of 16 (one resolution, inference): patchify_rect and the
+        attention that streams keys and values through LDS instead of the kernels instantiated for SIDES.  tap(i, x): called
+        after every block but a CLS-only last one with the residual stream the block left (without `save` the next block
+        overwrites it); reps_out: a [sum F, 384] view (any row stride) that receives reps instead of a new tensor."""
         f = self.flat
         imgs = list(img) if isinstance(img, (list, tuple)) else [img]
         dev = imgs[0].device
         groups, M, NP, Ftot = _row_groups(imgs)
-        if want_last_attn and len(groups) > 1:
+        if end == "probs" and len(groups) > 1:
             raise ValueError("get_last_selfattention takes one resolution")
         # Every decision of the pass, taken once; inside the loop only "is this the last block" is left.
         pl = SimpleNamespace(groups=groups, M=M, NP=NP, Ftot=Ftot, dev=dev, save=save, e16=_empty(torch.bfloat16, dev),
-                             e32=_empty(torch.float32, dev))
+                             e32=_empty(torch.float32, dev), streaming=streaming, reps_out=reps_out)
         # Large M (training step, big extraction batches): the N = 384 GEMMs run on the row-owning kernel with the
         # FOLLOWING LayerNorm in their epilogue (sais_gemm_ln_fwd): proj -> norm2, fc2 -> the next block's norm1.
         # Only block 0's norm1 and the final norm remain stand-alone launches.
@@ -453,16 +406,17 @@ class VisionTransformer(nn.Module):
         # the CLS-only tail runs its [frames, 384] GEMMs on the split-K small-M kernel (SAIS_EPI_RAW_SLABS_F32: M < 8192 only), so a
         # pass with 8192 or more FRAMES computes the last block on every row like the others (pruned=False is
         # recorded in `saved`, the backward follows it)
-        pl.prune = prune and self.prune_last_block and not want_last_attn and Ftot < ops.ROW_GEMM_MIN_M
+        pl.prune = end == "reps" and self.prune_last_block and Ftot < ops.ROW_GEMM_MIN_M
         pl.prune_q = pl.prune and len(groups) == 1 and _PRUNE_Q
-        pl.mlp_fused = ops.mlp_fused_enabled(M)
+        pl.mlp_fused = not streaming and ops.mlp_fused_enabled(M)      # (the streaming pass has never taken that switch)
         # One C call per Block (sais_vit_block_fwd: the launches of _block_fwd_launches, sequenced by the library) whenever
         # nothing needs the per-launch view: no HIP-event instrumentation (bench.py's roofline pass), one resolution group
-        # (and not the block whose probabilities get_last_selfattention returns)
-        pl.block_call = self.block_calls and ops.TIMER is None and len(groups) == 1 and fused and not pl.mlp_fused
+        # (and not the block whose probabilities get_last_selfattention returns); it sequences the resident attention
+        pl.block_call = self.block_calls and ops.TIMER is None and len(groups) == 1 and fused and not pl.mlp_fused \
+            and not streaming
         patches, x = self._embed_fwd(pl, imgs)
-        draw = self.training and self.drop_path_rate > 0 and not want_last_attn
-        dp = self._droppath_draw(groups, dev) if draw else None
+        draw = self.training and self.drop_path_rate > 0 and end != "probs" and not streaming
+        pl.dp = dp = self._droppath_draw(groups, dev) if draw else None
         saved = {"patches": patches, "blocks": [], "groups": groups, "M": M, "Ftot": Ftot, "dp": dp} if save else None
         b = ln1 = None                                   # the block's tensors; (xn, mean1, rstd1) of its norm1
         # norm1's outputs for a block: its own with `save`, else one xn for the whole pass and no statistics
@@ -474,6 +428,8 @@ class VisionTransformer(nn.Module):
                 ln1 = norm1_out()
                 ops.layernorm_fwd(x, M, D, f.w32(p + "norm1.weight"), f.w32(p + "norm1.bias"), 1e-6, y16=ln1[0], mean=ln1[1],
                                   rstd=ln1[2])
+            if end == "norm1" and last:
+                return ln1[0], None
             if pl.prune and last:                        # the CLS-only last block: its qkv here, the rest in _cls_tail_fwd
                 xn = ln1[0]
                 qkv = pl.e16(M, 3 * D) if save or b is None else b["qkv"]      # (with `save` it keeps its tensors itself)
@@ -487,14 +443,14 @@ class VisionTransformer(nn.Module):
                                 qkv.view(g0["Fr"], g0["ntok"], 3 * D)[:, 0, :D], bias=bq[:D])
                 else:
                     ops.gemm_nt(xn, Wq, L.EPI_BIAS_BF16, qkv, bias=bq)
-                reps, tail = self._cls_tail_fwd(f, i, x, *ln1, qkv, groups, dp, save, pl.e16, pl.e32, reps_out)
+                reps, tail = self._cls_tail_fwd(pl, i, x, ln1, qkv)
                 if save:
                     saved["blocks"].append(tail)
                     saved.update(x_final=tail["x_out"], meanN=tail["meanN"], rstdN=tail["rstdN"], pruned=True)
                 return reps, saved
             if save or b is None:                        # without `save` one set of tensors serves every block
                 b = self._block_buffers(pl, x, ln1)
-            if want_last_attn and last:
+            if end == "probs" and last:
                 return self._attn_fwd(pl, i, b, want_probs=True), None
             nxt = norm1_out() if fused and not last else None
             x_out = pl.e32(M, D) if save else x          # (without `save` the residual stream is updated in place)
@@ -512,7 +468,9 @@ class VisionTransformer(nn.Module):
             x, ln1 = x_out, nxt or ln1
             if tap is not None:
                 tap(i, x)
-        reps, meanN, rstdN = self._final_norm_fwd(pl, x, reps_out)
+        if end == "blocks":
+            return x, saved
+        reps, meanN, rstdN = self._final_norm_fwd(pl, x)
         if save:
             saved.update(x_final=x, meanN=meanN, rstdN=rstdN)
         return reps, saved
@@ -526,8 +484,8 @@ class VisionTransformer(nn.Module):
             Fr, ntok = g["Fr"], g["ntok"]
             pg = patches[g["prows"]]
             xg = x[g["rows"]].view(Fr, ntok, D)
-            ops.patchify(im, pg)
-            pos, g["interp"] = self._pos_table(im.shape[-1], pl.dev)
+            (ops.patchify_rect if pl.streaming else ops.patchify)(im, pg)
+            pos, g["interp"] = self._pos_table(im.shape[2], im.shape[3], pl.dev)
             ops.gemm_nt(pg, f.w("patch_embed.proj.weight").view(D, PATCH_K), L.EPI_PATCH_F32, xg,
                         bias=f.w32("patch_embed.proj.bias"), aux=pos, grp=(ntok - 1, ntok, 1))
             ops.vit_cls_rows(f.w32("cls_token"), pos, xg, Fr, ntok)
@@ -560,14 +518,18 @@ class VisionTransformer(nn.Module):
                     h=e16(M, HID) if save or not pl.block_call else None)
 
     def _attn_fwd(self, pl, i, b, want_probs=False):
-        """qkv and the attention of block i, per group.  want_probs: get_last_selfattention's exit — the attention also writes
+        """qkv and the attention of block i, per group: LDS-resident, or (pl.streaming) the one that takes any token count.  want_probs: get_last_selfattention's exit — the attention also writes
         its probabilities f32 [frames, heads, ntok, ntok], which are returned (one group)."""
         f, p, probs = self.flat, f"blocks.{i}.", None
         ops.gemm_nt(b["xn1"], f.w(p + "attn.qkv.weight"), L.EPI_BIAS_BF16, b["qkv"], bias=f.w32(p + "attn.qkv.bias"))
         for g, lg in zip(pl.groups, b["lse"]):
             if want_probs:
                 probs = pl.e32(g["Fr"], HEADS, g["ntok"], g["ntok"])
-            ops.vit_attn_fwd(b["qkv"][g["rows"]], g["Fr"], b["ao"][g["rows"]], lg, probs, ntok=g["ntok"])
+            qkv, ao = _rows(b["qkv"], g), _rows(b["ao"], g)
+            if pl.streaming:
+                ops.vit_attn_fwd_any(qkv, g["Fr"], g["ntok"], ao)
+            else:
+                ops.vit_attn_fwd(qkv, g["Fr"], ao, lg, probs, ntok=g["ntok"])
         return probs
 
     def _block_fwd_launches(self, pl, i, b, x_out, nxt, rs_attn, rs_mlp):
@@ -602,10 +564,10 @@ class VisionTransformer(nn.Module):
                 ops.gemm_nt(h, f.w(p + "mlp.fc2.weight"), L.EPI_BIAS_RESID_F32, x_out, bias=f.w32(p + "mlp.fc2.bias"),
                             aux=x_mid, rowscale=rs_mlp)
 
-    def _final_norm_fwd(self, pl, x, reps_out=None):
+    def _final_norm_fwd(self, pl, x):
         """The final norm on the CLS rows only (row stride = ntok * 384).  Returns (reps f32 [frames, 384], mean, rstd)."""
         f, Ftot = self.flat, pl.Ftot
-        reps = pl.e32(Ftot, D) if reps_out is None else reps_out
+        reps = pl.e32(Ftot, D) if pl.reps_out is None else pl.reps_out
         meanN, rstdN = (pl.e32(Ftot), pl.e32(Ftot)) if pl.save else (None, None)
         for g in pl.groups:
             fr = g["frames"]
@@ -622,12 +584,12 @@ class VisionTransformer(nn.Module):
             self._bp = (key, [ops.vit_block_params(f, j, self.depth) for j in range(self.depth)])
         return self._bp[1][i]
 
-    def _cls_tail_fwd(self, f, i, x, xn1, mean1, rstd1, qkv, groups, dp, save, e16, e32, reps_out=None):
+    def _cls_tail_fwd(self, pl, i, x, ln1, qkv):
         """The last block from its qkv on, restricted to what forward() returns (the CLS rows): attention for the CLS query
         (sais_vit_attn_cls_fwd, one launch per resolution group), then proj + residual, norm2, fc1 + GELU, fc2 + residual and
         the final norm on [frames, 384] tensors (all groups together).  The residual input is the strided view x[::ntok]."""
-        p = f"blocks.{i}."
-        Ftot = sum(g["Fr"] for g in groups)
+        f, p = self.flat, f"blocks.{i}."
+        groups, Ftot, dp, save, e16, e32 = pl.groups, pl.Ftot, pl.dp, pl.save, pl.e16, pl.e32
         ao = e16(Ftot, D)
         for g in groups:
             ops.vit_attn_cls_fwd(qkv[g["rows"]], g["Fr"], ao[g["frames"]], g["ntok"])
@@ -648,28 +610,25 @@ class VisionTransformer(nn.Module):
                     bias=f.w32(p + "mlp.fc1.bias"), out2=u)
         ops.gemm_nt_splitk(h, f.w(p + "mlp.fc2.weight"), 12, bias=f.w32(p + "mlp.fc2.bias"), rowscale=rs_mlp, aux=x_mid,
                            out32=x_out)
-        reps = e32(Ftot, D) if reps_out is None else reps_out
+        reps = e32(Ftot, D) if pl.reps_out is None else pl.reps_out
         meanN, rstdN = (e32(Ftot), e32(Ftot)) if save else (None, None)
         ops.layernorm_fwd(x_out, Ftot, D, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6, y32=reps, mean=meanN, rstd=rstdN,
                           ldy32=reps.stride(0))
-        tail = dict(cls=True, x_in=x, mean1=mean1, rstd1=rstd1, xn1=xn1, qkv=qkv, ao=ao, x_mid=x_mid, mean2=mean2, rstd2=rstd2,
+        tail = dict(cls=True, x_in=x, mean1=ln1[1], rstd1=ln1[2], xn1=ln1[0], qkv=qkv, ao=ao, x_mid=x_mid, mean2=mean2, rstd2=rstd2,
                     xn2=xn2, dgelu=u, h=h, rs_attn=rs_attn, rs_mlp=rs_mlp, x_out=x_out, meanN=meanN, rstdN=rstdN) if save else None
         return reps, tail
 
-    def _cls_tail_bwd(self, f, saved, dreps, dx, dxa, dqkv, fused, pend):
+    def _cls_tail_bwd(self, pl, saved, dreps, dx, dxa, dqkv, pend):
         """Backward of _cls_tail_fwd: the gradient enters on the CLS rows only.  Everything row-local stays on [frames, 384]
         tensors; the attention backward (sais_vit_attn_cls_bwd) writes the whole dqkv (dk, dv of every token, dq of the CLS
         rows, zeros elsewhere); the dX of qkv + norm1's backward then writes EVERY row of dx / dxa, taking the residual-stream
         gradient from the compact CLS tensor (dres_period) — no zero-filled [M, 384] buffer, no full-size cast.  With several
         resolution groups the two token-count-dependent launches run once per group on its rows."""
         i = self.depth - 1
-        p = f"blocks.{i}."
+        f, p = self.flat, f"blocks.{i}."
         s = saved["blocks"][i]
-        groups, M = saved["groups"], saved["M"]
-        Ftot = sum(g["Fr"] for g in groups)
-        dev = dreps.device
-        e16 = _empty(torch.bfloat16, dev)
-        dx_c = torch.empty(Ftot, D, dtype=torch.float32, device=dev)
+        groups, M, e16, Ftot = pl.groups, pl.M, pl.e16, saved["Ftot"]
+        dx_c = torch.empty(Ftot, D, dtype=torch.float32, device=dreps.device)
         ops.layernorm_bwd(s["x_out"], D, s["meanN"], s["rstdN"], f.w32("norm.weight"), Ftot, dy32=dreps, dx32=dx_c,
                           dgamma=f.g("norm.weight"), dbeta=f.g("norm.bias"))
         if self.grad_ready_hook:
@@ -705,7 +664,7 @@ class VisionTransformer(nn.Module):
             ops.gemm_tn_grouped([(dqkv, s["xn1"], gW, gb)], M)
         dp = saved.get("dp")
         rs_prev = None if dp is None or i == 0 else dp[2 * (i - 1) + 1]
-        if fused and all(g["Fr"] * g["ntok"] >= ops.ROW_GEMM_MIN_M for g in groups):
+        if pl.fused and all(g["Fr"] * g["ntok"] >= ops.ROW_GEMM_MIN_M for g in groups):
             for g in groups:
                 r = g["rows"]
                 ops.gemm_ln_bwd(dqkv[r], f.wt16[p + "attn.qkv.weight"], s["x_in"][r], s["mean1"][r], s["rstd1"][r],
@@ -760,7 +719,7 @@ class VisionTransformer(nn.Module):
                             dao=None if block_call else e16(M, D))
         if pruned:                                  # every row of dx is WRITTEN by the last block's dX qkv + norm1' kernel
             dx = torch.empty(M, D, dtype=torch.float32, device=dev)
-            self._cls_tail_bwd(f, saved, dreps, dx, dxa, t.dqkv, fused, pend)
+            self._cls_tail_bwd(pl, saved, dreps, dx, dxa, t.dqkv, pend)
         else:
             dx = torch.zeros(M, D, dtype=torch.float32, device=dev)
             self._final_norm_bwd(saved, dreps, dx, dxa)

@@ -109,6 +109,28 @@ def test_dense_features_vs_golden(vit, golden):
             assert err <= FEAT_REL * scale, (name, j, err, scale)
 
 
+def test_dense_features_at_the_row_kernel_dispatch(vit, golden):
+    """30 frames x 274 tokens = 8220 rows: the N = 384 GEMMs run on the row-owning kernel with the following LayerNorm in their
+    epilogue, and the taps read the stream those launches left.  A frame's features do not depend on the frames beside it, so the
+    two golden frames of d208x336, in front of 28 others, are held to their record at the bar of test_dense_features_vs_golden."""
+    from sais_amd import ops
+    name, H, W, n, seed = vos_ref.DENSE_CASES[1]
+    x = dev(np.concatenate([vos_ref.dense_input(H, W, seed), vos_ref.dense_input(H, W, 233, frames=28)]))
+    ntok = 1 + (H // 16) * (W // 16)
+    assert (name, ntok, n) == ("d208x336", 274, 2) and x.shape[0] * ntok >= ops.ROW_GEMM_MIN_M
+    got = vit.dense_features(x, n)
+    assert len(got) == n and all(t.shape == (30, ntok, 384) and t.dtype == torch.float32 for t in got)
+    ref = golden("vos")[name]
+    for j in range(n):
+        a = host(got[j][:2])[:, vos_ref.DENSE_ROWS]
+        err, scale = float(np.abs(a.astype(np.float64) - ref[j]).max()), float(np.abs(ref[j]).max())
+        print(f"{name} in 30 frames, layer {j}: max err {err:.3e} = {err / scale:.3e} max|ref|")
+        parity.parity_log("vos_dense_rowkernel_" + name, err / scale, FEAT_REL)
+        assert err <= FEAT_REL * scale, (name, j, err, scale)
+    again = vit.dense_features(x, n)
+    assert all(torch.equal(a, b) for a, b in zip(again, got))
+
+
 def test_dense_features_at_224_and_forward_untouched(vit):
     x = synth.clips(seed=10, B=1, T=2)[0].to(DEV)
     with torch.no_grad():

@@ -389,6 +389,38 @@ def _add_vit_cases():
     case("vit train 48 frames block_calls=0")(lambda dev: vit(dev, 48, False, True))
     case("vit eval 6 frames")(lambda dev: vit(dev, 6, True, False))
 
+    def frozen(dev, call, frames, H=224, W=224, depth=12):
+        """One inference entry of the frozen backbone; 48 frames of 160 x 272 or of 224 x 224 are past the row-kernel dispatch."""
+        import torch
+        from sais_amd.vit import vit_small
+        m = vit_small(depth=depth).to(dev).eval()
+        with torch.no_grad():
+            call(m, torch.zeros(frames, 3, H, W).to(dev))
+
+    for name, frames, H, W, n in (("2 x 160x272 n=2", 2, 160, 272, 2), ("48 x 160x272 n=2", 48, 160, 272, 2),
+                                  ("2 x 224x224 n=1", 2, 224, 224, 1), ("2 x 208x336 n=2", 2, 208, 336, 2)):
+        case("vit dense_features " + name)(lambda dev, a=(frames, H, W), n=n: frozen(dev, lambda m, x: m.dense_features(x, n), *a))
+    for name, frames, H, W, depth in (("2 x 64x96", 2, 64, 96, 12), ("48 x 224x224", 48, 224, 224, 12),
+                                      ("2 x 64x96 depth=1", 2, 64, 96, 1)):
+        case("vit cls_attention " + name)(lambda dev, a=(frames, H, W, depth): frozen(dev, lambda m, x: m.cls_attention(x), *a))
+    for frames in (2, 48):
+        case("vit get_intermediate_layers n=2 %d frames" % frames)(
+            lambda dev, frames=frames: frozen(dev, lambda m, x: m.get_intermediate_layers(x, 2), frames))
+    case("vit probe_features n=4 2 frames")(lambda dev: frozen(dev, lambda m, x: m.probe_features(x, 4), 2))
+    case("vit probe_features avgpool 2 frames")(lambda dev: frozen(dev, lambda m, x: m.probe_features(x, 1, avgpool=True), 2))
+    for side in (224, 96):
+        case("vit get_last_selfattention 2 x %dx%d" % (side, side))(
+            lambda dev, side=side: frozen(dev, lambda m, x: m.get_last_selfattention(x), 2, side, side))
+
+    @case("vit two resolutions, no save")
+    def _(dev):
+        import torch
+        from sais_amd.vit import vit_small
+        m = vit_small().to(dev).eval()
+        m._engine(dev)
+        with torch.no_grad():
+            m._forward_kernels([torch.zeros(2, 3, 224, 224).to(dev), torch.zeros(3, 3, 96, 96).to(dev)], save=False)
+
 
 # ------------------------------------------------------------------------------------------------ driver
 def run(root, out, real):
