@@ -155,7 +155,8 @@ int sais_gemm_tn_grouped(const SaisTnItem* items, int nitems, int M, int nsplit,
  * training size) the M-splits store their raw 192 x 384 partial tiles into `slabs` (plain 16-B stores) and a second launch sums
  * them in a FIXED order into dW / db: no fp32 atomics (10 splits x 7.1 MB of them per ViT block otherwise, ~50 us of the launch),
  * bit-reproducible weight gradients.  sais_gemm_tn_grouped_slab_bytes returns the bytes that launch uses (0: no slab form applies
- * and `slabs` is ignored); slabs 16-B aligned; NULL = fp32 atomics.  Environment, read once per process: SAIS_TN_XL = 0 selects
+ * and `slabs` is ignored); slabs 16-B aligned; NULL = fp32 atomics; fewer bytes than that = SAIS_ERR_ARG.  The query and the launch
+ * read ONE plan (csrc/tn_plan.hpp: form, tiles, M-splits, slab bytes), so they cannot disagree.  Environment, read once per process: SAIS_TN_XL = 0 selects
  * the 128 x 384 kernel of rounds 2-5 (whose own slab form stays opt-in: SAIS_TN_SLABS = 1), SAIS_TN_XL = 8 the eight-wave form
  * of the large tile, SAIS_TN_XL_SLABS = 0 its atomics (LABNOTES R6.1).                                                      */
 size_t sais_gemm_tn_grouped_slab_bytes(const SaisTnItem* items, int nitems, int M);

@@ -7,14 +7,12 @@
 // LayerNorm kernels run behind plain GEMMs.  Both give the reference's Block; only the launch count differs.
 #include <string.h>
 #include "common.hpp"
+#include "tn_plan.hpp"
+#include "ws_layout.hpp"
 #include "../../include/sais_hip.h"
 
 namespace {
-constexpr int D = 384, HID = 1536, QKV = 1152;
 constexpr int ROW_GEMM_MIN_M = 8192;
-constexpr size_t ALIGN = 256;
-
-size_t up(size_t b) { return (b + ALIGN - 1) / ALIGN * ALIGN; }
 
 int gemm(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, const float* bias, void* out, int ldo,
          void* out2, int ldo2, const void* aux, int ldaux, const float* rowscale, void* stream) {
@@ -26,61 +24,36 @@ int gemm(const void* A, int lda, const void* B, int ldb, int M, int N, int K, in
 }
 
 #define TRY(x) do { int rc_ = (x); if (rc_ != SAIS_OK) return rc_; } while (0)
-}  // namespace
 
-// slab workspace of the block's grouped weight-gradient launch (sais_gemm_tn_grouped_ws; 0 outside its wide-tile regime)
-static size_t block_dw_slab_bytes(int M) {
+// workspace of one backward call; its slab region is what the block's grouped dW launch asks for (0 outside the slab forms): the one size query
+VitBwdLayout block_bwd_layout(size_t M) {
     const SaisTnItem shape[4] = {{nullptr, D, nullptr, HID, D, HID, nullptr, HID, nullptr},
                                  {nullptr, HID, nullptr, D, HID, D, nullptr, D, nullptr},
                                  {nullptr, D, nullptr, D, D, D, nullptr, D, nullptr},
                                  {nullptr, QKV, nullptr, D, QKV, D, nullptr, D, nullptr}};
-    return sais_gemm_tn_grouped_slab_bytes(shape, 4, M);
+    return vit_bwd_layout(M, sais_gemm_tn_grouped_slab_bytes(shape, 4, (int)M));
 }
+}  // namespace
 
 extern "C" size_t sais_workspace_bytes(int op, int frames, int ntok) {
     if (frames <= 0 || ntok <= 0) return 0;
     const size_t M = (size_t)frames * ntok;
     switch (op) {
-        case SAIS_OP_VIT_BLOCK_FWD:                    // GELU(u) when the caller does not keep it (inference)
-            return up(M * HID * 2);
-        case SAIS_OP_VIT_BLOCK_BWD:                    // du, d(mid) bf16, d(attention out), dqkv, dxn (small-M regime), dW slabs
-            return up(M * HID * 2) + 3 * up(M * D * 2) + up(M * QKV * 2) + up(block_dw_slab_bytes((int)M));
-        case SAIS_OP_TEMPORAL_LAYER_FWD: {             // raw split-K slabs of out_proj, then of linear2 (the larger)
-            const int m = frames * ntok;
-            const int ns = sais_tgemm_nsplit(m, D, 2048) > sais_tgemm_nsplit(m, D, D) ? sais_tgemm_nsplit(m, D, 2048)
-                                                                                       : sais_tgemm_nsplit(m, D, D);
-            return up((size_t)ns * M * D * 4);
-        }
-        case SAIS_OP_TEMPORAL_LAYER_BWD: {             // dy2, dt2, dy-drop1, dh, dqkv + the slabs of dh . W1 / dt1 . Wo
-            const int m = frames * ntok;
-            const size_t slabs = (size_t)(sais_tgemm_nsplit(m, D, 2048) + sais_tgemm_nsplit(m, D, D)) * M * D * 4;
-            return 3 * up(M * D * 4) + up(M * 2048 * 4) + up(M * QKV * 4) + up(slabs);
-        }
-        default:
-            return 0;
+        case SAIS_OP_VIT_BLOCK_FWD: return ws_up(M * HID * 2);                    // GELU(u) when the caller does not keep it (inference)
+        case SAIS_OP_VIT_BLOCK_BWD: return block_bwd_layout(M).total;
+        case SAIS_OP_TEMPORAL_LAYER_FWD: return temporal_fwd_layout(M).total;
+        case SAIS_OP_TEMPORAL_LAYER_BWD: return temporal_bwd_layout(M).total;
+        default: return 0;
     }
 }
 
 namespace {
-// scratch of one backward call (sais_workspace_bytes(SAIS_OP_VIT_BLOCK_BWD)): the gradient tensors that live inside the block
-struct BwdScratch { void* du; void* dxb; void* dao; void* dxn; void* dqkv; void* slabs; };
-BwdScratch carve(void* workspace, int M) {
-    char* ws = (char*)workspace;
-    BwdScratch s;
-    s.du = ws;             ws += up((size_t)M * HID * 2);
-    s.dxb = ws;            ws += up((size_t)M * D * 2);
-    s.dao = ws;            ws += up((size_t)M * D * 2);
-    s.dxn = ws;            ws += up((size_t)M * D * 2);
-    s.dqkv = ws;           ws += up((size_t)M * QKV * 2);
-    s.slabs = ws;
-    return s;
-}
 // the four weight / bias gradients of a block as items of the grouped dW launch
-void dw_items(const SaisVitBlockParams* w, const SaisVitBlockBwd* a, const BwdScratch& sc, SaisTnItem* items) {
+void dw_items(const SaisVitBlockParams* w, const SaisVitBlockBwd* a, char* ws, const VitBwdLayout& l, SaisTnItem* items) {
     items[0] = SaisTnItem{a->dx16_in, D, a->h, HID, D, HID, w->d_fc2_w, HID, w->d_fc2_b};
-    items[1] = SaisTnItem{sc.du, HID, a->xn2, D, HID, D, w->d_fc1_w, D, w->d_fc1_b};
-    items[2] = SaisTnItem{sc.dxb, D, a->attn_out, D, D, D, w->d_proj_w, D, w->d_proj_b};
-    items[3] = SaisTnItem{sc.dqkv, QKV, a->xn1, D, QKV, D, w->d_qkv_w, D, w->d_qkv_b};
+    items[1] = SaisTnItem{ws + l.du, HID, a->xn2, D, HID, D, w->d_fc1_w, D, w->d_fc1_b};
+    items[2] = SaisTnItem{ws + l.dxb, D, a->attn_out, D, D, D, w->d_proj_w, D, w->d_proj_b};
+    items[3] = SaisTnItem{ws + l.dqkv, QKV, a->xn1, D, QKV, D, w->d_qkv_w, D, w->d_qkv_b};
 }
 // M-splits for the kernels that take the number from the caller (the 192 x 384 kernel plans its own)
 int dw_nsplit(int M, int nblocks) {
@@ -161,13 +134,12 @@ extern "C" int sais_vit_block_bwd(const SaisVitBlockParams* w, const SaisVitBloc
     if (!w->qkv_wt || !w->proj_wt || !w->fc1_wt || !w->fc2_wt || !w->norm1_g || !w->norm2_g || !w->d_qkv_w || !w->d_proj_w ||
         !w->d_fc1_w || !w->d_fc2_w || !w->d_norm1_g || !w->d_norm1_b || !w->d_norm2_g || !w->d_norm2_b)
         return SAIS_ERR_ARG;
-    if (!workspace || ws_bytes < sais_workspace_bytes(SAIS_OP_VIT_BLOCK_BWD, a->frames, a->ntok) || ((uintptr_t)workspace & 15))
-        return SAIS_ERR_ARG;
     const int M = a->frames * a->ntok;
-    const BwdScratch sc = carve(workspace, M);
-    void* const du = sc.du; void* const dxb = sc.dxb; void* const dao = sc.dao; void* const dxn = sc.dxn; void* const dqkv = sc.dqkv;
-    void* const slabs = sc.slabs;
-    const size_t slab_bytes = block_dw_slab_bytes(M);
+    const VitBwdLayout l = block_bwd_layout((size_t)a->frames * a->ntok);
+    if (!workspace || ws_bytes < l.total || ((uintptr_t)workspace & 15)) return SAIS_ERR_ARG;
+    char* const ws = (char*)workspace;
+    void* const du = ws + l.du; void* const dxb = ws + l.dxb; void* const dao = ws + l.dao; void* const dxn = ws + l.dxn;
+    void* const dqkv = ws + l.dqkv;
     if (a->defer_dw && a->dx16_in == a->dx16_out) return SAIS_ERR_ARG;
     const bool fused = M >= ROW_GEMM_MIN_M;
     // MLP branch: du = (d . W2) * GELU'(u);  d(norm2 out) = du . W1;  norm2's backward adds the residual gradient
@@ -193,8 +165,8 @@ extern "C" int sais_vit_block_bwd(const SaisVitBlockParams* w, const SaisVitBloc
     // the four weight / bias gradients of the block in one launch
     if (!a->defer_dw) {
         SaisTnItem items[4];
-        dw_items(w, a, sc, items);
-        TRY(sais_gemm_tn_grouped_ws(items, 4, M, dw_nsplit(M, 1), slab_bytes ? slabs : nullptr, slab_bytes, stream));
+        dw_items(w, a, ws, l, items);
+        TRY(sais_gemm_tn_grouped_ws(items, 4, M, dw_nsplit(M, 1), l.slab_bytes ? ws + l.slabs : nullptr, l.slab_bytes, stream));
     }
     // dX of qkv + norm1's backward: the gradient of the block input
     if (fused) {
@@ -221,25 +193,24 @@ extern "C" int sais_vit_blocks_dw(const SaisVitBlockParams* const* w, const Sais
         return SAIS_ERR_ARG;
     SaisTnItem items[SAIS_TN_MAX_ITEMS];
     const int M = a[0] ? a[0]->frames * a[0]->ntok : 0;
+    if (M <= 0) return SAIS_ERR_ARG;
+    const VitBwdLayout l = block_bwd_layout((size_t)a[0]->frames * a[0]->ntok);
+    if (ws_bytes < l.total) return SAIS_ERR_ARG;
     for (int i = 0; i < nblocks; ++i) {
-        if (!w[i] || !a[i] || !workspaces[i] || a[i]->frames * a[i]->ntok != M || M <= 0) return SAIS_ERR_ARG;
-        if (ws_bytes < sais_workspace_bytes(SAIS_OP_VIT_BLOCK_BWD, a[i]->frames, a[i]->ntok)) return SAIS_ERR_ARG;
-        dw_items(w[i], a[i], carve(workspaces[i], M), items + 4 * i);
+        if (!w[i] || !a[i] || !workspaces[i] || a[i]->frames * a[i]->ntok != M) return SAIS_ERR_ARG;
+        dw_items(w[i], a[i], (char*)workspaces[i], l, items + 4 * i);
     }
-    // partial tiles of the M-splits go to the slab region of the first workspace when it is large enough (it is sized for one block at
-    // ten splits = 240 partial tiles; two blocks at five, five at two are as many); otherwise fp32 atomics
     for (int i = 0; i < nextra; ++i) items[4 * nblocks + i] = extra[i];
-    const int n = 4 * nblocks + nextra;
-    const size_t need = sais_gemm_tn_grouped_slab_bytes(items, n, M);
-    const size_t have = block_dw_slab_bytes(M);
-    void* slabs = need && need <= have ? carve(workspaces[0], M).slabs : nullptr;
-    return sais_gemm_tn_grouped_ws(items, n, M, dw_nsplit(M, nblocks), slabs, slabs ? have : 0, stream);
+    // partial tiles of the M-splits go to the slab region of the first workspace when the plan of these items uses it (it is sized for one
+    // block at ten splits = 240 partial tiles; two blocks at five, five at two are as many); too small or no slab form: fp32 atomics
+    const int n = 4 * nblocks + nextra, nsplit = dw_nsplit(M, nblocks);
+    int64_t plan[6] = {0};
+    const bool slab = sais_gemm_tn_plan_(items, n, M, nsplit, (int64_t)l.slab_bytes, 0, plan) == SAIS_OK && plan[5];
+    return sais_gemm_tn_grouped_ws(items, n, M, nsplit, slab ? (char*)workspaces[0] + l.slabs : nullptr, slab ? l.slab_bytes : 0, stream);
 }
 
 // ---------------------------------------------------------------------------------------------- temporal encoder layer
 namespace {
-constexpr int FF = 2048;
-
 int tg(const float* A, const float* W, int M, int N, int K, int epi, int nsplit, const float* bias, const float* aux, float* out,
        float p, const unsigned long long* rng, unsigned site, void* stream) {
     SaisTGemm g;
@@ -258,24 +229,22 @@ extern "C" int sais_temporal_layer_fwd(const SaisTemporalLayerParams* w, const S
     if (!w->in_proj_w || !w->out_proj_w || !w->linear1_w || !w->linear2_w || !w->norm1_g || !w->norm1_b || !w->norm2_g || !w->norm2_b)
         return SAIS_ERR_ARG;
     if (a->p_drop < 0.f || a->p_drop >= 1.f || (a->p_drop > 0.f && !a->rng_state)) return SAIS_ERR_ARG;
-    if (!workspace || ws_bytes < sais_workspace_bytes(SAIS_OP_TEMPORAL_LAYER_FWD, a->B, a->S) || ((uintptr_t)workspace & 15))
-        return SAIS_ERR_ARG;
     const int M = a->B * a->S;
+    const TemporalFwdLayout l = temporal_fwd_layout((size_t)a->B * a->S);
+    if (!workspace || ws_bytes < l.total || ((uintptr_t)workspace & 15)) return SAIS_ERR_ARG;
     float* slabs = (float*)workspace;
     const float p = a->p_drop;
     const unsigned long long* rng = p > 0.f ? a->rng_state : nullptr;
     // self-attention: in_proj -> per (sequence, head) softmax(q k^T / sqrt(96)) v with key-padding mask -> out_proj
     TRY(tg(a->z, w->in_proj_w, M, QKV, D, SAIS_TG_BIAS, 1, w->in_proj_b, nullptr, a->qkv, 0.f, nullptr, 0, stream));
     TRY(sais_temporal_attn_fwd(a->qkv, a->key_pad, a->B, a->S, a->ctx, a->attn_avg, p, rng, a->site0, stream));
-    int ns = sais_tgemm_nsplit(M, D, D);
-    TRY(tg(a->ctx, w->out_proj_w, M, D, D, SAIS_TG_RAW, ns, nullptr, nullptr, slabs, 0.f, nullptr, 0, stream));
-    TRY(sais_temporal_ln_fwd(slabs, ns, (long)M * D, w->out_proj_b, a->z, M, p, rng, a->site0 + 1, a->y1, w->norm1_g, w->norm1_b,
+    TRY(tg(a->ctx, w->out_proj_w, M, D, D, SAIS_TG_RAW, l.ns_out, nullptr, nullptr, slabs, 0.f, nullptr, 0, stream));
+    TRY(sais_temporal_ln_fwd(slabs, l.ns_out, (long)M * D, w->out_proj_b, a->z, M, p, rng, a->site0 + 1, a->y1, w->norm1_g, w->norm1_b,
                              1e-5f, a->z1, a->mean1, a->rstd1, stream));
     // feed-forward
     TRY(tg(a->z1, w->linear1_w, M, FF, D, SAIS_TG_BIAS_RELU, 1, w->linear1_b, nullptr, a->h, p, rng, a->site0 + 2, stream));
-    ns = sais_tgemm_nsplit(M, D, FF);
-    TRY(tg(a->h, w->linear2_w, M, D, FF, SAIS_TG_RAW, ns, nullptr, nullptr, slabs, 0.f, nullptr, 0, stream));
-    TRY(sais_temporal_ln_fwd(slabs, ns, (long)M * D, w->linear2_b, a->z1, M, p, rng, a->site0 + 3, a->y2, w->norm2_g, w->norm2_b,
+    TRY(tg(a->h, w->linear2_w, M, D, FF, SAIS_TG_RAW, l.ns_ff, nullptr, nullptr, slabs, 0.f, nullptr, 0, stream));
+    TRY(sais_temporal_ln_fwd(slabs, l.ns_ff, (long)M * D, w->linear2_b, a->z1, M, p, rng, a->site0 + 3, a->y2, w->norm2_g, w->norm2_b,
                              1e-5f, a->z_out, a->mean2, a->rstd2, stream));
     return SAIS_OK;
 }
@@ -291,33 +260,27 @@ extern "C" int sais_temporal_layer_bwd(const SaisTemporalLayerParams* w, const S
         !w->d_out_proj_w || !w->d_linear1_w || !w->d_linear2_w || !w->d_norm1_g || !w->d_norm1_b || !w->d_norm2_g || !w->d_norm2_b)
         return SAIS_ERR_ARG;
     if (a->p_drop < 0.f || a->p_drop >= 1.f || (a->p_drop > 0.f && !a->rng_state)) return SAIS_ERR_ARG;
-    if (!workspace || ws_bytes < sais_workspace_bytes(SAIS_OP_TEMPORAL_LAYER_BWD, a->B, a->S) || ((uintptr_t)workspace & 15))
-        return SAIS_ERR_ARG;
     const int M = a->B * a->S;
+    const TemporalBwdLayout l = temporal_bwd_layout((size_t)a->B * a->S);
+    if (!workspace || ws_bytes < l.total || ((uintptr_t)workspace & 15)) return SAIS_ERR_ARG;
     const float p = a->p_drop;
     const unsigned long long* rng = p > 0.f ? a->rng_state : nullptr;
-    char* ws = (char*)workspace;
-    float* dy2 = (float*)ws;   ws += up((size_t)M * D * 4);
-    float* dt2 = (float*)ws;   ws += up((size_t)M * D * 4);          // dropout2's backward of dy2 (p = 0: dy2 itself is used)
-    float* dt1 = (float*)ws;   ws += up((size_t)M * D * 4);
-    float* dh = (float*)ws;    ws += up((size_t)M * FF * 4);
-    float* dqkv = (float*)ws;  ws += up((size_t)M * QKV * 4);
-    float* slab1 = (float*)ws;                                        // dh . W1   [ns1][M][384]
-    const int ns1 = sais_tgemm_nsplit(M, D, FF), nso = sais_tgemm_nsplit(M, D, D), nsq = sais_tgemm_nsplit(M, D, QKV);
-    float* slabo = slab1 + (size_t)ns1 * M * D;                       // dt1 . Wo  [nso][M][384]
+    char* const ws = (char*)workspace;
+    float* dy2 = (float*)(ws + l.dy2), *dt2 = (float*)(ws + l.dt2), *dt1 = (float*)(ws + l.dt1), *dh = (float*)(ws + l.dh);
+    float* dqkv = (float*)(ws + l.dqkv), *slab1 = (float*)(ws + l.slab1), *slabo = (float*)(ws + l.slabo);
     // norm2 backward (the gradient of the layer output arrives as slabs + add), dropout2 backward as a second output
     float* g2 = p > 0.f ? dt2 : dy2;
     TRY(sais_temporal_ln_bwd(a->dz_slabs, a->dz_slabs ? a->nslab : 0, a->slab_stride, a->dz_add, a->y2, a->mean2, a->rstd2,
                              w->norm2_g, M, dy2, p > 0.f ? dt2 : nullptr, p, rng, a->site0 + 3, w->d_norm2_g, w->d_norm2_b, stream));
     // FFN: dh = drop'(relu'(.)) (g2 . W2);  d(norm1 out) = dh . W1 + dy2 (residual): left as slabs + add for norm1's backward
     TRY(tg(g2, w->linear2_wt, M, FF, D, SAIS_TG_DRELU, 1, nullptr, a->h, dh, p, rng, a->site0 + 2, stream));
-    TRY(tg(dh, w->linear1_wt, M, D, FF, SAIS_TG_RAW, ns1, nullptr, nullptr, slab1, 0.f, nullptr, 0, stream));
+    TRY(tg(dh, w->linear1_wt, M, D, FF, SAIS_TG_RAW, l.ns1, nullptr, nullptr, slab1, 0.f, nullptr, 0, stream));
     float* g1 = p > 0.f ? dt1 : a->dx_add;
-    TRY(sais_temporal_ln_bwd(slab1, ns1, (long)M * D, dy2, a->y1, a->mean1, a->rstd1, w->norm1_g, M, a->dx_add,
+    TRY(sais_temporal_ln_bwd(slab1, l.ns1, (long)M * D, dy2, a->y1, a->mean1, a->rstd1, w->norm1_g, M, a->dx_add,
                              p > 0.f ? dt1 : nullptr, p, rng, a->site0 + 1, w->d_norm1_g, w->d_norm1_b, stream));
     // attention: d ctx = g1 . Wo (raw slabs, summed on load by the attention backward)
-    TRY(tg(g1, w->out_proj_wt, M, D, D, SAIS_TG_RAW, nso, nullptr, nullptr, slabo, 0.f, nullptr, 0, stream));
-    TRY(sais_temporal_attn_bwd(a->qkv, a->key_pad, a->B, a->S, slabo, nso, (long)M * D, dqkv, p, rng, a->site0, stream));
+    TRY(tg(g1, w->out_proj_wt, M, D, D, SAIS_TG_RAW, l.nso, nullptr, nullptr, slabo, 0.f, nullptr, 0, stream));
+    TRY(sais_temporal_attn_bwd(a->qkv, a->key_pad, a->B, a->S, slabo, l.nso, (long)M * D, dqkv, p, rng, a->site0, stream));
     // the four weight / bias gradients of the layer in one launch (one M-split: owner-computes, no atomics)
     SaisTnItem items[4] = {
         {g2, D, a->h, FF, D, FF, w->d_linear2_w, FF, w->d_linear2_b},
@@ -330,6 +293,6 @@ extern "C" int sais_temporal_layer_bwd(const SaisTemporalLayerParams* w, const S
         TRY(sais_gemm_tn_grouped_f32(items, 4, M, 1, stream));
     }
     // gradient wrt the layer input = dx_add (residual path, written by norm1's backward) + dqkv . Win (raw slabs)
-    TRY(tg(dqkv, w->in_proj_wt, M, D, QKV, SAIS_TG_RAW, nsq, nullptr, nullptr, a->dx_slabs, 0.f, nullptr, 0, stream));
+    TRY(tg(dqkv, w->in_proj_wt, M, D, QKV, SAIS_TG_RAW, l.nsq, nullptr, nullptr, a->dx_slabs, 0.f, nullptr, 0, stream));
     return SAIS_OK;
 }

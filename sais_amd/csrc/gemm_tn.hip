@@ -8,11 +8,10 @@
 // half-wave touches per read fall on distinct banks.  Split over M (gridDim.z) with fp32
 // atomicAdd of the partial tiles; db via one extra MFMA column of ones in the n2-tile-0 blocks.
 #include "common.hpp"
-#include "../../include/sais_hip.h"
+#include "tn_plan.hpp"
 
 namespace {
 
-constexpr int TK = 64;                 // m rows per step
 constexpr int TROW = 288;              // padded LDS row bytes (128 bf16 + 16 pad)
 constexpr int TTILE = TK * TROW;       // 18 KiB
 
@@ -282,15 +281,10 @@ __global__ __launch_bounds__(256) void gemm_tn_grouped_f32_kernel(TnGroup gp) {
 // launch, DMA-only 223 us vs 166 us of MFMA work); this tile needs a third fewer fill bytes per flop: 64 KiB per
 // 64-row step (P 16 KiB + three 128-column blocks of Q) for 2 x 128 x 384 x 64 flop.  Two 64-KiB stages = 128 KiB of
 // LDS, one workgroup per CU; 36 tiles x 7 M-splits = 252 workgroups fill the 256 CUs in one round.
-constexpr int WQ = 384;
 constexpr int WBLK = 64 * 256;                 // one 64-row x 128-column block, 16 KiB
 constexpr int WSTAGE = 4 * WBLK;               // P block + 3 Q blocks
 
-struct TnWideGroup {
-    TnParams item[SAIS_TN_MAX_ITEMS];
-    int tile_end[SAIS_TN_MAX_ITEMS];
-    int nitems, ntiles;
-};
+struct TnWideGroup : TnGroup {};                 // the same items and prefix sums, in 128 x 384 tiles
 
 // The wide dW kernel: 128 x 384 tile, 8 waves (2 x 4 of 64 x 96), global -> VGPR -> LDS staging (a plain vector load does
 // not hold the wave the way an LDS-DMA issue does) with two tiles in flight in registers (a first-touch row slab comes
@@ -566,49 +560,37 @@ __global__ __launch_bounds__(256) void tn_slab_finish_kernel(TnWideGroup gp, con
 
 }  // namespace
 
-extern "C" int sais_gemm_tn_xl_(const SaisTnItem* items, int nitems, int M, int nwaves, void* slabs, size_t slab_bytes, void* stream);   // gemm_tn_xl.hip: 192 x 384 dW tiles
-extern "C" size_t sais_gemm_tn_xl_slab_bytes_(const SaisTnItem* items, int nitems, int M, int nwaves);
-// SAIS_TN_XL = 4 | 8 waves (default 4), 0 = the 128 x 384 kernel; SAIS_TN_XL_SLABS = 0: fp32 atomics instead of slabs + finish;
-// SAIS_TN_SLABS = 1: the round-5 slab form of the 128 x 384 kernel (implies SAIS_TN_XL = 0)
-static bool tn_old_slabs() {
-    static const bool v = sais_env_int("SAIS_TN_SLABS", 0) != 0;
-    return v;
-}
-static int tn_xl_waves() {
-    static const int v = tn_old_slabs() ? 0 : sais_env_int("SAIS_TN_XL", 4);
-    return v;
-}
-static bool tn_xl_slabs() {
-    static const bool v = sais_env_int("SAIS_TN_XL_SLABS", 1) != 0;
+// SAIS_TN_XL = 4 | 8 waves (default 4; 8 in experimental builds only), 0 = the 128 x 384 kernel; SAIS_TN_XL_SLABS = 0: fp32 atomics
+// instead of slabs + finish; SAIS_TN_SLABS = 1: the round-5 slab form of the 128 x 384 kernel (implies SAIS_TN_XL = 0).  Once per process.
+static const TnSwitches& tn_switches() {
+    static const bool old_slabs = sais_env_int("SAIS_TN_SLABS", 0) != 0;
+    static const int xl = old_slabs ? 0 : sais_env_int("SAIS_TN_XL", 4);
+    static const TnSwitches v = {SAIS_EXPERIMENTAL || !xl ? xl : 4, sais_env_int("SAIS_TN_XL_SLABS", 1) != 0, old_slabs};
     return v;
 }
 CLK_EXPORT(gemm_tn)
 
-// M rows cut into at most nsplit slices of `rows` rows, a whole number of TK-row steps each; ns = slices that hold rows
-struct TnSplit { int rows, ns; };
-static TnSplit tn_split(int M, int nsplit) {
-    const int rows = ((M + nsplit - 1) / nsplit + TK - 1) / TK * TK;
-    return {rows, (M + rows - 1) / rows};
-}
-
-// items -> the 128 x 128 tiles of one grouped launch; align = leading-dimension multiple of the operands (8 for bf16, 4 for fp32)
-static bool tn_fill_group(TnGroup& gp, const SaisTnItem* items, int nitems, int M, int rows, int align) {
-    gp.nitems = nitems;
-    gp.ntiles = 0;
+// argument check of the grouped launches; align = leading-dimension multiple of the operands (8 for bf16, 4 for fp32; 0: shapes only)
+static bool tn_items_ok(const SaisTnItem* items, int nitems, int M, int nsplit, int align) {
+    if (!items || nitems <= 0 || nitems > SAIS_TN_MAX_ITEMS || M <= 0 || nsplit <= 0) return false;
     for (int i = 0; i < nitems; ++i) {
         const SaisTnItem& t = items[i];
-        if (!t.P || !t.Q || !t.dW || t.N1 % 128 || t.N2 % 128 || t.ldp % align || t.ldq % align) return false;
-        gp.item[i] = TnParams{t.P, t.Q, t.ldp, t.ldq, M, t.N1, t.N2, t.dW, t.ldw, t.db, rows};
-        gp.ntiles += (t.N1 / 128) * (t.N2 / 128);
-        gp.tile_end[i] = gp.ntiles;
+        if (t.N1 % 128 || t.N2 % 128 || (align && (!t.P || !t.Q || !t.dW || t.ldp % align || t.ldq % align))) return false;
     }
     return true;
 }
 
-// the 128 x 384 kernel: one workgroup per CU, so as many M-splits of wt tiles as keep the grid within one round of 256
-static TnSplit tn_wide_split(int M, int wt) { return tn_split(M, 256 / wt < 1 ? 1 : 256 / wt); }
-// its slab workspace: every workgroup's raw fp32 tile (8 waves x 24 accumulator tiles x 64 lanes x 16 B) and 128 bias sums
-static size_t tn_wide_slab_bytes(int wt, int wns) { return (size_t)wt * wns * (8 * 24 * 64 * 16 + 128 * 4); }
+// items -> the tp x tq tiles of one grouped launch
+template <class Group>
+static Group tn_group(const SaisTnItem* items, int nitems, int M, int rows, int tp, int tq) {
+    Group gp; gp.nitems = nitems; gp.ntiles = 0;
+    for (int i = 0; i < nitems; ++i) {
+        const SaisTnItem& t = items[i];
+        gp.item[i] = TnParams{t.P, t.Q, t.ldp, t.ldq, M, t.N1, t.N2, t.dW, t.ldw, t.db, rows};
+        gp.tile_end[i] = gp.ntiles += (t.N1 / tp) * (t.N2 / tq);
+    }
+    return gp;
+}
 
 static int launch_tn(const void* P, int ldp, const void* Q, int ldq, int M, int N1, int N2, float* dW, int ldw,
                      float* db, int nsplit, void* stream, bool f32) {
@@ -622,20 +604,20 @@ static int launch_tn(const void* P, int ldp, const void* Q, int ldq, int M, int 
 }
 
 extern "C" size_t sais_gemm_tn_grouped_slab_bytes(const SaisTnItem* items, int nitems, int M) {
-    if (!items || nitems <= 0 || nitems > SAIS_TN_MAX_ITEMS) return 0;
-    if (tn_xl_waves()) {
-        const size_t need = tn_xl_slabs() ? sais_gemm_tn_xl_slab_bytes_(items, nitems, M, tn_xl_waves()) : 0;
-        if (need) return need;
-    }
-    // the 128 x 384 kernel's slab form is opt-in (SAIS_TN_SLABS = 1): without the switch no workspace is asked for
-    if (!tn_old_slabs() || M % TK || M < 8192) return 0;
-    int wt = 0;
-    for (int i = 0; i < nitems; ++i) {
-        if (items[i].N1 % 128 || items[i].N2 % WQ) return 0;
-        wt += (items[i].N1 / 128) * (items[i].N2 / WQ);
-    }
-    const int wns = tn_wide_split(M, wt).ns;
-    return wns > 1 ? tn_wide_slab_bytes(wt, wns) : 0;
+    if (!items || nitems <= 0 || nitems > SAIS_TN_MAX_ITEMS || M <= 0) return 0;
+    return tn_plan(items, nitems, M, 1, TN_ANY_SLABS, tn_switches()).slab_bytes;
+}
+
+// The plan of a launch without making it (no GPU; not in the ABI): of sais_gemm_tn_grouped_f32 (f32 != 0), else of _ws for an offer of bytes
+// (< 0: no slabs).  out = TnForm, tiles, M-splits, rows per split, workgroups, slab bytes used.  SAIS_ERR_ARG: refused shapes, offer too small
+extern "C" int sais_gemm_tn_plan_(const SaisTnItem* items, int nitems, int M, int nsplit, int64_t slab_bytes_offered, int f32,
+                                  int64_t out[6]) {
+    if (!tn_items_ok(items, nitems, M, nsplit, 0) || !out) return SAIS_ERR_ARG;
+    const TnPlan pl = f32 ? tn_plan_f32(items, nitems, M, nsplit)
+                          : tn_plan(items, nitems, M, nsplit, slab_bytes_offered < 0 ? TN_NO_SLABS : slab_bytes_offered, tn_switches());
+    const int64_t v[6] = {pl.form, pl.tiles, pl.nsplit, pl.rows, pl.workgroups, (int64_t)pl.slab_bytes};
+    for (int i = 0; i < 6; ++i) out[i] = v[i];
+    return pl.short_offer ? SAIS_ERR_ARG : SAIS_OK;
 }
 
 extern "C" int sais_gemm_tn_grouped(const SaisTnItem* items, int nitems, int M, int nsplit, void* stream) {
@@ -645,75 +627,52 @@ extern "C" int sais_gemm_tn_grouped(const SaisTnItem* items, int nitems, int M, 
 extern "C" int sais_gemm_tn_grouped_ws(const SaisTnItem* items, int nitems, int M, int nsplit, void* slabs, size_t slab_bytes,
                                        void* stream) {
     SAIS_ENTER();
-    if (!items || nitems <= 0 || nitems > SAIS_TN_MAX_ITEMS || M <= 0 || nsplit <= 0) return SAIS_ERR_ARG;
-    const TnSplit sp = tn_split(M, nsplit);
-    TnGroup gp;
-    if (!tn_fill_group(gp, items, nitems, M, sp.rows, 8)) return SAIS_ERR_ARG;
-    // large tiles (192 x 384, gemm_tn_xl.hip) when every N1 % 192 == 0, N2 % 384 == 0 and M % 32 == 0
-    if (tn_xl_waves()) {
-        const bool sl = slabs != nullptr && tn_xl_slabs();
-        const int r = sais_gemm_tn_xl_(items, nitems, M, tn_xl_waves(), sl ? slabs : nullptr, sl ? slab_bytes : 0, stream);
-        if (r != 0) return r > 0 ? SAIS_OK : r;
-    }
-    // wide tiles (128 x 384) when every item allows them and M is a whole number of 64-row steps
-    bool wide = M % TK == 0 && M >= 8192;
-    for (int i = 0; i < nitems && wide; ++i) wide = items[i].N2 % WQ == 0;
-    if (wide) {
-        TnWideGroup wg;
-        wg.nitems = nitems;
-        int wt = 0;
-        for (int i = 0; i < nitems; ++i) {
-            wt += (items[i].N1 / 128) * (items[i].N2 / WQ);
-            wg.tile_end[i] = wt;
-        }
-        wg.ntiles = wt;
-        const TnSplit ws = tn_wide_split(M, wt);
-        const int wns = ws.ns;
-        for (int i = 0; i < nitems; ++i) { wg.item[i] = gp.item[i]; wg.item[i].rows_per_split = ws.rows; }
-        if (!sais_dyn_lds_once<gemm_tn_pp_kernel<false>>(2 * WSTAGE) || !sais_dyn_lds_once<gemm_tn_pp_kernel<true>>(2 * WSTAGE))
-            return SAIS_ERR_LAUNCH;
-        // opt-in (SAIS_TN_SLABS=1): bit-reproducible weight gradients.  Measured SLOWER than the atomics (LABNOTES R5.1: 254 vs 240 us
-        // stand-alone, 12.86 vs 12.76 ms per step) — the atomic tail this was built to remove is not there.
-        if (slabs && wns > 1 && tn_old_slabs()) {
-            if (slab_bytes < tn_wide_slab_bytes(wt, wns) || ((uintptr_t)slabs & 15)) return SAIS_ERR_ARG;
-            hipLaunchKernelGGL(gemm_tn_pp_kernel<true>, dim3(wt * wns), dim3(512), 2 * WSTAGE, (hipStream_t)stream, wg, (float*)slabs);
-            hipLaunchKernelGGL(tn_slab_finish_kernel, dim3(wt * (8 * 24 * 64) / 256 + (wt * 128 + 255) / 256), dim3(256), 0, (hipStream_t)stream, wg, (const float*)slabs, wns);
-        } else {
+    if (!tn_items_ok(items, nitems, M, nsplit, 8)) return SAIS_ERR_ARG;
+    const int64_t offer = !slabs ? TN_NO_SLABS : slab_bytes > (size_t)INT64_MAX ? INT64_MAX : (int64_t)slab_bytes;
+    const TnPlan pl = tn_plan(items, nitems, M, nsplit, offer, tn_switches());
+    if (pl.short_offer || (pl.slab_bytes && ((uintptr_t)slabs & 15))) return SAIS_ERR_ARG;
+    const hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(pl.workgroups);
+    switch (pl.form) {
+        case TN_XL_SLAB: case TN_XL_ATOMIC:
+            return sais_tn_xl_launch(pl, items, nitems, M, tn_switches().xl_waves, pl.form == TN_XL_SLAB ? (float*)slabs : nullptr, stream);
+        case TN_WIDE_SLAB: case TN_WIDE_ATOMIC: {
+            const TnWideGroup wg = tn_group<TnWideGroup>(items, nitems, M, pl.rows, 128, WQ);
+            if (!sais_dyn_lds_once<gemm_tn_pp_kernel<false>>(2 * WSTAGE) || !sais_dyn_lds_once<gemm_tn_pp_kernel<true>>(2 * WSTAGE))
+                return SAIS_ERR_LAUNCH;
 #if SAIS_EXPERIMENTAL
             static const int tn_ni = sais_env_int("SAIS_TN_NI", 4);
-            if (tn_ni == 2) {
+            if (tn_ni == 2 && pl.form == TN_WIDE_ATOMIC) {
                 if (!sais_dyn_lds_once<gemm_tn_pp_kernel<false, 2>>(2 * WSTAGE)) return SAIS_ERR_LAUNCH;
-                hipLaunchKernelGGL((gemm_tn_pp_kernel<false, 2>), dim3(wt * wns), dim3(512), 2 * WSTAGE, (hipStream_t)stream, wg, (float*)nullptr);
-            } else
+                hipLaunchKernelGGL((gemm_tn_pp_kernel<false, 2>), grid, dim3(512), 2 * WSTAGE, st, wg, (float*)nullptr);
+                break;
+            }
 #endif
-            hipLaunchKernelGGL(gemm_tn_pp_kernel<false>, dim3(wt * wns), dim3(512), 2 * WSTAGE, (hipStream_t)stream, wg, (float*)nullptr);
+            // the slab form is opt-in (SAIS_TN_SLABS=1): bit-reproducible weight gradients.  Measured SLOWER than the atomics (LABNOTES
+            // R5.1: 254 vs 240 us stand-alone, 12.86 vs 12.76 ms per step) — the atomic tail this was built to remove is not there.
+            if (pl.form == TN_WIDE_SLAB) {
+                hipLaunchKernelGGL(gemm_tn_pp_kernel<true>, grid, dim3(512), 2 * WSTAGE, st, wg, (float*)slabs);
+                hipLaunchKernelGGL(tn_slab_finish_kernel, dim3(pl.tiles * (8 * 24 * 64) / 256 + (pl.tiles * 128 + 255) / 256), dim3(256), 0, st, wg, (const float*)slabs, pl.nsplit);
+            } else hipLaunchKernelGGL(gemm_tn_pp_kernel<false>, grid, dim3(512), 2 * WSTAGE, st, wg, (float*)nullptr);
+            break;
         }
-        return sais_check_launch();
+        default: {
+            const TnGroup gp = tn_group<TnGroup>(items, nitems, M, pl.rows, 128, 128);
+            hipLaunchKernelGGL(gemm_tn_grouped_kernel, grid, dim3(256), 0, st, gp);
+        }
     }
-    hipLaunchKernelGGL(gemm_tn_grouped_kernel, dim3(gp.ntiles * sp.ns), dim3(256), 0, (hipStream_t)stream, gp);
     return sais_check_launch();
 }
 
 extern "C" int sais_gemm_tn_grouped_f32(const SaisTnItem* items, int nitems, int M, int nsplit, void* stream) {
     SAIS_ENTER();
-    if (!items || nitems <= 0 || nitems > SAIS_TN_MAX_ITEMS || M <= 0 || nsplit <= 0) return SAIS_ERR_ARG;
-    const TnSplit sp = tn_split(M, nsplit);
-    TnGroup gp;
-    if (!tn_fill_group(gp, items, nitems, M, sp.rows, 4)) return SAIS_ERR_ARG;
-    const int total = gp.ntiles;
-    if (sp.ns == 1 && total < 200) {
-        // one M-split and fewer tiles than CUs (the temporal layers: 132): 64-row dW tiles = twice the workgroups
-        int t64 = 0;
-        for (int i = 0; i < nitems; ++i) {
-            t64 += (items[i].N1 / 64) * (items[i].N2 / 128);
-            gp.tile_end[i] = t64;
-        }
-        gp.ntiles = t64;
-        hipLaunchKernelGGL((gemm_tn_grouped_f32_kernel<true, 64>), dim3(t64), dim3(256), 0, (hipStream_t)stream, gp);
-        return sais_check_launch();
-    }
-    if (sp.ns == 1) hipLaunchKernelGGL(gemm_tn_grouped_f32_kernel<true>, dim3(total), dim3(256), 0, (hipStream_t)stream, gp);
-    else hipLaunchKernelGGL(gemm_tn_grouped_f32_kernel<false>, dim3(total * sp.ns), dim3(256), 0, (hipStream_t)stream, gp);
+    if (!tn_items_ok(items, nitems, M, nsplit, 4)) return SAIS_ERR_ARG;
+    const TnPlan pl = tn_plan_f32(items, nitems, M, nsplit);
+    const dim3 grid(pl.workgroups); const hipStream_t st = (hipStream_t)stream;
+    const TnGroup gp = tn_group<TnGroup>(items, nitems, M, pl.rows, pl.form == TN_F32_OWNER64 ? 64 : 128, 128);
+    if (pl.form == TN_F32_OWNER64) hipLaunchKernelGGL((gemm_tn_grouped_f32_kernel<true, 64>), grid, dim3(256), 0, st, gp);
+    else if (pl.form == TN_F32_OWNER128) hipLaunchKernelGGL(gemm_tn_grouped_f32_kernel<true>, grid, dim3(256), 0, st, gp);
+    else hipLaunchKernelGGL(gemm_tn_grouped_f32_kernel<false>, grid, dim3(256), 0, st, gp);
     return sais_check_launch();
 }
 

@@ -28,13 +28,13 @@
 #include <type_traits>
 #include <utility>
 #include "common.hpp"
-#include "../../include/sais_hip.h"
+#include "tn_plan.hpp"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
-constexpr int XP = 192, XQ = 384, XK = 32, XNST = 4;
+constexpr int XNST = 4;
 constexpr int XPROW = XP * 2, XQROW = XQ * 2;              // image row bytes
 constexpr int XPIMG = XK * XPROW;                          // 12 KiB
 constexpr int XQIMG = XK * XQROW;                          // 24 KiB
@@ -430,64 +430,32 @@ __global__ __launch_bounds__(256) void xl_finish_kernel(XlGroup gp, const float*
 
 }  // namespace
 
-// Applies when every item has N1 % 192 == 0 and N2 % 384 == 0, M % 32 == 0 and every split gets a worthwhile number of steps
-// (a launch with 4 tiles would be 64 splits of 24 steps, each flushing a whole tile: the 128 x 384 kernel is faster there).
-static bool xl_plan(const SaisTnItem* items, int nitems, int M, XlGroup& gp) {
-    if (M % XK || M < 8192 || nitems > SAIS_TN_MAX_ITEMS) return false;
-    int nt = 0;
+// The launch of the XL form of `pl` (tn_plan.hpp decides when it applies): fills XlGroup from the items.
+template <int NW, bool SLAB>
+static int xl_launch(const TnPlan& pl, const SaisTnItem* items, int nitems, int M, float* slabs, hipStream_t stream) {
+    // the slabs were sized by tn_plan(), perhaps in an object built with other flags: this kernel's own size must be the plan's
+    if (SLAB && pl.slab_bytes != pl.workgroups * xl_slab_bytes_per_wg(NW)) return SAIS_ERR_ARG;
+    if (!sais_dyn_lds_once<gemm_tn_xl_kernel<NW, SLAB>>(XLDS)) return SAIS_ERR_LAUNCH;
+    XlGroup gp; gp.nitems = nitems; gp.ntiles = 0; gp.nsteps = M / XK; gp.nsplit = pl.nsplit;
     for (int i = 0; i < nitems; ++i) {
         const SaisTnItem& t = items[i];
-        if (t.N1 % XP || t.N2 % XQ || t.ldp % 8 || t.ldq % 8) return false;
-        if (((uintptr_t)t.P & 15) || ((uintptr_t)t.Q & 15)) return false;
         gp.item[i] = XlItem{(const bf16*)t.P, (const bf16*)t.Q, t.dW, t.db, t.ldp, t.ldq, t.ldw, t.N2 / XQ};
-        nt += (t.N1 / XP) * (t.N2 / XQ);
-        gp.tile_end[i] = nt;
+        gp.tile_end[i] = gp.ntiles += (t.N1 / XP) * (t.N2 / XQ);
     }
-    gp.nitems = nitems;
-    gp.ntiles = nt;
-    gp.nsteps = M / XK;
-    const int ns = 256 / nt < 1 ? 1 : 256 / nt;
-    if (gp.nsteps / ns < 48) return false;
-    gp.nsplit = ns;
-    return true;
-}
-
-static size_t xl_slab_need(const XlGroup& gp, int nwaves) {
-    if (!SAIS_EXPERIMENTAL) nwaves = 4;
-    const int nt_wave = nwaves == 8 ? 9 : 18;
-    const size_t nwg = (size_t)gp.ntiles * gp.nsplit;
-    return nwg * nwaves * nt_wave * 4 * 64 * 16 + nwg * nwaves * 4 * 64 * 16;
-}
-
-// bytes of slab workspace the launch would use (0: the regime does not apply)
-extern "C" size_t sais_gemm_tn_xl_slab_bytes_(const SaisTnItem* items, int nitems, int M, int nwaves) {
-    XlGroup gp;
-    if (!xl_plan(items, nitems, M, gp) || gp.nsplit < 2) return 0;
-    return xl_slab_need(gp, nwaves);
-}
-
-template <int NW, bool SLAB>
-static int xl_launch(const XlGroup& gp, float* slabs, hipStream_t stream) {
-    if (!sais_dyn_lds_once<gemm_tn_xl_kernel<NW, SLAB>>(XLDS)) return SAIS_ERR_LAUNCH;
-    const int nwg = gp.ntiles * gp.nsplit;
+    const int nwg = pl.workgroups;
     hipLaunchKernelGGL((gemm_tn_xl_kernel<NW, SLAB>), dim3(nwg), dim3(64 * NW), XLDS, stream, gp, slabs);
     if constexpr (SLAB) {
         constexpr int NT = NW == 8 ? 9 : 18;
         const int nbody = gp.ntiles * (NW * NT * 4 * 64) / 256, nbias = (gp.ntiles * 2 * 4 * 64 + 255) / 256;
         hipLaunchKernelGGL(xl_finish_kernel<NW>, dim3(nbody + nbias), dim3(256), 0, stream, gp, (const float*)slabs, nwg);
     }
-    return sais_check_launch() == SAIS_OK ? 1 : SAIS_ERR_LAUNCH;
+    return sais_check_launch();
 }
 
-// Returns 1 when the launch was made, 0 when the regime does not apply (caller falls back), < 0 on error.
-// slabs (16-B aligned, >= sais_gemm_tn_xl_slab_bytes_) selects the atomics-free form; NULL = fp32 atomics.
-extern "C" int sais_gemm_tn_xl_(const SaisTnItem* items, int nitems, int M, int nwaves, void* slabs, size_t slab_bytes, void* stream) {
-    XlGroup gp;
-    if (!xl_plan(items, nitems, M, gp)) return 0;
-    const bool slab = slabs != nullptr && gp.nsplit >= 2;
-    if (slab && (slab_bytes < xl_slab_need(gp, nwaves) || ((uintptr_t)slabs & 15))) return SAIS_ERR_ARG;
+int sais_tn_xl_launch(const TnPlan& pl, const SaisTnItem* items, int nitems, int M, int nwaves, float* slabs, void* stream) {
+    const hipStream_t st = (hipStream_t)stream;
 #if SAIS_EXPERIMENTAL      // the eight-wave form of the same tile (two waves per SIMD, compiler-scheduled): slower, LABNOTES R6.1
-    if (nwaves == 8) return slab ? xl_launch<8, true>(gp, (float*)slabs, (hipStream_t)stream) : xl_launch<8, false>(gp, nullptr, (hipStream_t)stream);
+    if (nwaves == 8) return slabs ? xl_launch<8, true>(pl, items, nitems, M, slabs, st) : xl_launch<8, false>(pl, items, nitems, M, nullptr, st);
 #endif
-    return slab ? xl_launch<4, true>(gp, (float*)slabs, (hipStream_t)stream) : xl_launch<4, false>(gp, nullptr, (hipStream_t)stream);
+    return slabs ? xl_launch<4, true>(pl, items, nitems, M, slabs, st) : xl_launch<4, false>(pl, items, nitems, M, nullptr, st);
 }

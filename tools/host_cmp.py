@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Do two builds of libsais_hip.so answer the same on the host?  No GPU needed: the slab-workspace sizing rule of the grouped
-weight-gradient launch under its environment switches, and the return codes of the sais_gemm_* entries for bad arguments
+weight-gradient launch under its environment switches, the block workspace sizes, and the return codes of the sais_gemm_* entries for bad arguments
 (the calls of tests/test_abi.py).  Every (library, environment) pair runs in a child process of its own, because the
 switches are read once per process.
     tools/host_cmp.py <libA.so> <libB.so>      exit status 1 on any difference"""
@@ -11,9 +11,15 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ITEM_SETS = {"vit block": ((384, 1536), (1536, 384), (384, 384), (1152, 384)), "two items": ((384, 384), (1152, 384)),
-             "N2 % 384 != 0": ((384, 1536), (1536, 512))}
-MS = (300, 8192, 50432)
+BLOCK = ((384, 1536), (1536, 384), (384, 384), (1152, 384))
+KV = ((768, 384),)
+# the edges of every regime of the grouped dW launch: 192 x 384 tiles (N1 % 192, N2 % 384, M % 32, >= 48 steps per split, one or
+# several splits), 128 x 384 tiles (M % 64, M >= 8192), 128 x 128 tiles; more items than SAIS_TN_MAX_ITEMS
+ITEM_SETS = {"vit block": BLOCK, "two items": ((384, 384), (1152, 384)), "N2 % 384 != 0": ((384, 1536), (1536, 512)),
+             "k/v only": KV, "6 blocks + k/v": BLOCK * 6 + KV, "10 blocks + k/v": BLOCK * 10 + KV, "49 items": ((384, 384),) * 49,
+             "fc1 + fc2": BLOCK[:2], "N1 % 192 != 0": ((128, 384),)}
+MS = (300, 3152, 8192, 12608, 12640, 50432, 100864)
+WS_SHAPES = ((64, 197), (256, 197), (16, 37), (8, 16), (204, 16))          # (frames, ntok) for sais_workspace_bytes, all four ops
 ENVS = ({}, {"SAIS_TN_XL": "0"}, {"SAIS_TN_XL": "8"}, {"SAIS_TN_XL_SLABS": "0"}, {"SAIS_TN_SLABS": "1"})
 
 
@@ -32,6 +38,10 @@ def child():
             it.N1, it.N2 = n1, n2
         for M in MS:
             out[f"slab_bytes {label} M={M}"] = lib.sais_gemm_tn_grouped_slab_bytes(items, len(shapes), M)
+    lib.sais_workspace_bytes.restype = ctypes.c_size_t
+    for frames, ntok in WS_SHAPES:
+        for op in range(4):
+            out[f"workspace_bytes op={op} ({frames}, {ntok})"] = lib.sais_workspace_bytes(op, frames, ntok)
     items = (_lib.SaisTnItem * 4)()
     out["slab_bytes NULL items"] = lib.sais_gemm_tn_grouped_slab_bytes(None, 4, 50432)
     out["slab_bytes 0 items"] = lib.sais_gemm_tn_grouped_slab_bytes(items, 0, 50432)
