@@ -1,0 +1,93 @@
+#!/usr/bin/env python3
+"""Image retrieval on revisited Oxford / Paris with a DINO checkpoint on MI355X — the command line and result lines of the
+reference's SAIS/scripts/dino-main/eval_image_retrieval.py, driving sais_amd.retrieval (hand-written gfx950 kernels: the backbone
+at every image's own resolution, the bilinear rescaling of --multiscale, and the ranks of the listed positives and junk images
+instead of an argsort of the whole database).
+
+    python SAIS/scripts/dino-main/eval_image_retrieval.py --data_path <revisited_paris_oxford root> --dataset roxford5k \
+        --pretrained_weights <checkpoint.pth> [--multiscale 1] [--imsize 224]
+
+Kept: every flag, `gnd_<dataset>.pkl`, `img.thumbnail((imsize, imsize), LANCZOS)` + ImageNet normalisation (on Pillow in the
+DataLoader workers), batch size 1 (images keep their aspect ratio, so their sizes differ), the Medium / Hard groupings, and the
+lines ">> <dataset>: mAP M: .., H: .." and ">> <dataset>: mP@k[ 1  5 10] M: .., H: ..".
+Differences: only `--arch vit_small --patch_size 16` (anything else is refused with a message); without `--pretrained_weights`
+the weights stay random and the script says so (no download of the Google-Landmarks checkpoint); one process (WORLD_SIZE > 1
+exits, as eval_knn.py here); `--dist_url` / `--local_rank` / `--use_cuda` are accepted and ignored; sides that are no multiple of
+16 are cropped at the right and bottom to the multiple below, which is what the reference's patch embedding computes; equal
+similarities rank in ascending database index; `--dump_features <dir>` (new) saves the normalised features.
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", ".."))
+from sais_amd import retrieval  # noqa: E402
+from sais_amd.model_io import bool_flag, load_dino_backbone  # noqa: E402
+
+
+def get_args_parser():
+    parser = argparse.ArgumentParser('Image Retrieval on revisited Paris and Oxford')
+    parser.add_argument('--data_path', default='/path/to/revisited_paris_oxford/', type=str)
+    parser.add_argument('--dataset', default='roxford5k', type=str, choices=['roxford5k', 'rparis6k'])
+    parser.add_argument('--multiscale', default=False, type=bool_flag)
+    parser.add_argument('--imsize', default=224, type=int, help='Image size')
+    parser.add_argument('--pretrained_weights', default='', type=str, help="Path to pretrained weights to evaluate.")
+    parser.add_argument('--use_cuda', default=True, type=bool_flag,
+                        help="Accepted for compatibility: the features always stay on the GPU.")
+    parser.add_argument('--arch', default='vit_small', type=str, help='Architecture (vit_small only)')
+    parser.add_argument('--patch_size', default=16, type=int, help='Patch resolution of the model (16 only).')
+    parser.add_argument("--checkpoint_key", default="teacher", type=str,
+                        help='Key to use in the checkpoint (example: "teacher")')
+    parser.add_argument('--num_workers', default=10, type=int, help='Number of data loading workers per GPU.')
+    parser.add_argument("--dist_url", default="env://", type=str, help="Accepted and ignored.")
+    parser.add_argument("--local_rank", default=0, type=int, help="Accepted and ignored.")
+    parser.add_argument('--dump_features', default=None, help='Directory for trainfeat.pth / queryfeat.pth (normalised features)')
+    return parser
+
+
+def main(argv=None):
+    args = get_args_parser().parse_args(argv)
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        sys.exit("eval_image_retrieval.py runs as one process on one GPU: multi-rank feature extraction is not implemented "
+                 "(start it without a distributed launcher)")
+    if args.arch.replace("deit", "vit") != "vit_small" or args.patch_size != 16:
+        sys.exit(f"Architecture {args.arch} / patch size {args.patch_size} not supported: this path runs --arch vit_small "
+                 "--patch_size 16 only")
+    print("\n".join("%s: %s" % (k, str(v)) for k, v in sorted(dict(vars(args)).items())))
+    dev = torch.device("cuda:0")
+
+    # ============ preparing data ... ============
+    dataset_train = retrieval.OxfordParisDataset(args.data_path, args.dataset, split="train", imsize=args.imsize)
+    dataset_query = retrieval.OxfordParisDataset(args.data_path, args.dataset, split="query", imsize=args.imsize)
+    loader = lambda ds: torch.utils.data.DataLoader(ds, batch_size=1, num_workers=args.num_workers, pin_memory=True,
+                                                    drop_last=False, shuffle=False)
+    print(f"train: {len(dataset_train)} imgs / query: {len(dataset_query)} imgs")
+
+    # ============ building network ... ============
+    print(f"Model {args.arch} {args.patch_size}x{args.patch_size} built.")
+    model = load_dino_backbone(args, dev)
+    cls = retrieval.cls_features(model)
+    fn = (lambda x: retrieval.multi_scale(x, cls)) if args.multiscale else cls
+
+    # Step 1: extract features, normalize
+    train_features = retrieval.l2_normalize(retrieval.extract_features(fn, loader(dataset_train), dev))
+    query_features = retrieval.l2_normalize(retrieval.extract_features(fn, loader(dataset_query), dev))
+    if args.dump_features:
+        os.makedirs(args.dump_features, exist_ok=True)
+        torch.save(train_features.cpu(), os.path.join(args.dump_features, "trainfeat.pth"))
+        torch.save(query_features.cpu(), os.path.join(args.dump_features, "queryfeat.pth"))
+
+    # Step 2: similarity (query x database); Step 3: evaluate from the ranks of the listed images
+    sim = retrieval.similarity(query_features, train_features)
+    ks = [1, 5, 10]
+    (mapM, mprM), (mapH, mprH) = retrieval.evaluate_revisited(sim, dataset_train.gnd, ks)
+    print('>> {}: mAP M: {}, H: {}'.format(args.dataset, np.around(mapM * 100, decimals=2), np.around(mapH * 100, decimals=2)))
+    print('>> {}: mP@k{} M: {}, H: {}'.format(args.dataset, np.array(ks), np.around(mprM * 100, decimals=2),
+                                              np.around(mprH * 100, decimals=2)))
+
+
+if __name__ == '__main__':
+    main()

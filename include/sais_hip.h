@@ -883,6 +883,46 @@ int sais_attn_render(const float* p, long ldp, const unsigned char* keep /*optio
                      int nheads, int h, int w, int n, int patch, const unsigned char* lut, float* heat,
                      unsigned char* rgb /*optional*/, float* workspace, void* stream);
 
+/* ================================================================ copy detection and image retrieval
+ * (dino-main/eval_copy_detection.py and eval_image_retrieval.py; sais_amd/csrc/retrieval.hip, host: VisionTransformer.
+ * retrieval_features and sais_amd/retrieval.py).  Additive entries: the ABI version does not change.  No atomics, every sum in one
+ * fixed order: every entry is bit-reproducible.
+ * sais_vit_cls_gem_norm: the Copydays descriptor (eval_copy_detection.py:166-175), the sibling of sais_vit_cls_avgpool_norm.
+ *   x f32 [frames][ntok, dim] (frame_stride floats apart) is the residual stream after the last block; LayerNorm (gamma, beta,
+ *   eps) of all ntok rows, then y[f][0 : dim] = norm(x)[f][0] (the CLS token: a sais_layernorm_fwd launch, so its bits) and
+ *   y[f][dim + j] = (mean over the ntok - 1 patch rows of max(norm(x)[f][1..][j], p_clamp_min)^4)^(1/4): GeM with exponent 4 as
+ *   two squarings and two square roots, the patch half in fp64 from the f32 inputs to one final rounding and summed in a fixed order, the halves CONCATENATED as the reference's torch.cat(dim=1) does.  y f32, ldy >= 2 dim
+ *   floats between frames.  Any ntok >= 2, dim == 384, p_clamp_min > 0.  The normed [frames, ntok, dim] tensor is not written.
+ * sais_colmean_cov: X f32 [N, D] (row stride ldx) -> mean f32 [D] = column means and cov f32 [D, D] = X^T X / N, UNCENTRED as
+ *   eval_copy_detection.py:283 computes it.  D % 64 == 0, D <= SAIS_COV_MAX_DIM, any N >= 1.  The exact f32-input MFMA: per element
+ *   an fmaf chain over the rows of a split in ascending order; the splits store raw partial tiles, a second launch adds them in
+ *   ascending order and divides by N.  Only the tiles on or above the diagonal are computed, the others are their mirror image:
+ *   cov is bit-symmetric.  workspace: sais_colmean_cov_workspace_bytes(N, D) bytes (0 for a shape the entry rejects); the query
+ *   and the launch read one plan.
+ * sais_center_rows: x[r][0 : dim] -= mean in place (database -= mean_feature, :279-280), x f32 [rows, dim] with row stride ldx,
+ *   dim % 4 == 0, 16-B aligned.
+ * sais_rank_positions: sim f32 [Nq, Ndb] (row stride ld), finite; offsets i32 [Nq + 1] and items i32 [offsets[Nq]] on the
+ *   device: per query a list of database indices (CSR).  pos[t] = the 0-based position of items[t] in its query's row under the
+ *   order (value descending, index ascending) = #{i : s[i] > s[j] or (s[i] == s[j] and i < j)}, which is
+ *   np.argsort(-s, kind="stable") — the positions utils.compute_map looks up with np.in1d (eval_image_retrieval.py:176).  The row
+ *   is streamed once per chunk of 64 listed items; a query with an empty list does no work; an item outside [0, Ndb) gets -1.
+ *   Integer and exact.  Ndb <= 2^30.  offsets must be non-decreasing with offsets[0] >= 0 and offsets[Nq] <= the length of items and
+ *   pos: they are device data and are NOT checked (a decreasing pair is read as an empty list; an offset past the arrays is read
+ *   out of bounds).  sais_amd.retrieval.rank_positions builds them from host lists and checks the items; a direct caller owns that.
+ * sais_resize_bilinear_f32: F.interpolate(x, scale_factor=scale, mode="bilinear", align_corners=False) of utils.multi_scale on
+ *   x f32 [frames, 3, H, W] -> y f32 [frames, 3, Ho, Wo] with Ho = floor(H scale), Wo = floor(W scale) (checked).  The source
+ *   coordinate is (float)(1 / scale) (dst + 0.5) - 0.5 clamped at 0: the given scale factor, as torch uses it with
+ *   recompute_scale_factor = None.                                                                                       */
+#define SAIS_COV_MAX_DIM 1536
+int sais_vit_cls_gem_norm(const float* x, long frame_stride, int frames, int ntok, int dim, const float* gamma, const float* beta,
+                          float eps, float p_clamp_min, float* y, long ldy, void* stream);
+size_t sais_colmean_cov_workspace_bytes(int N, int D);
+int sais_colmean_cov(const float* X, long ldx, int N, int D, float* mean, float* cov, void* workspace, size_t workspace_bytes,
+                     void* stream);
+int sais_center_rows(float* x, long ldx, long rows, int dim, const float* mean, void* stream);
+int sais_rank_positions(const float* sim, long ld, int Nq, int Ndb, const int* offsets, const int* items, int* pos, void* stream);
+int sais_resize_bilinear_f32(const float* x, int frames, int H, int W, double scale, float* y, int Ho, int Wo, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

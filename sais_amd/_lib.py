@@ -267,6 +267,14 @@ SIGNATURES = {
     "sais_attn_mass_mask": [c_void_p, c_long, c_int, c_int, ctypes.c_double, c_void_p, c_void_p],
     "sais_attn_render": [c_void_p, c_long, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                          c_void_p, c_void_p, c_void_p],
+    # copy detection and image retrieval
+    "sais_vit_cls_gem_norm": [c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_float, c_void_p, c_long,
+                              c_void_p],
+    "sais_colmean_cov_workspace_bytes": [c_int, c_int],
+    "sais_colmean_cov": [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p],
+    "sais_center_rows": [c_void_p, c_long, c_long, c_int, c_void_p, c_void_p],
+    "sais_rank_positions": [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "sais_resize_bilinear_f32": [c_void_p, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_int, c_int, c_void_p],
 }
 
 _lib = None
@@ -296,6 +304,7 @@ def load():
     lib.sais_augment_workspace_bytes.restype = ctypes.c_size_t
     lib.sais_gemm_tn_grouped_slab_bytes.restype = ctypes.c_size_t
     lib.sais_knn_workspace_bytes.restype = ctypes.c_size_t
+    lib.sais_colmean_cov_workspace_bytes.restype = ctypes.c_size_t
     lib.sais_last_error.restype = ctypes.c_char_p
     lib.sais_last_error.argtypes = []
     _lib = lib

@@ -31,21 +31,22 @@ def _features(t, name):
 
 class KnnIndex:
     """The train side of the classifier: features [Nt, D] (L2-normalised rows) split once into their bf16x3 image, labels
-    [Nt] (int64 or int32) in [0, num_classes)."""
+    [Nt] (int64 or int32) in [0, num_classes).  train_labels = None: an index for `search` alone (sais_amd.retrieval)."""
 
-    def __init__(self, train_features, train_labels, num_classes=1000):
+    def __init__(self, train_features, train_labels=None, num_classes=1000):
         f = _features(train_features, "train_features")
-        if not isinstance(train_labels, torch.Tensor) or not train_labels.is_cuda:
-            raise ValueError("train_labels: expected a device tensor")
-        if train_labels.dim() != 1 or train_labels.shape[0] != f.shape[0] or train_labels.dtype not in (torch.int64, torch.int32):
-            raise ValueError("train_labels: expected one int64 / int32 label per train row")
-        if not 1 <= num_classes <= MAX_CLASSES:
-            raise ValueError(f"num_classes must be in [1, {MAX_CLASSES}]")
-        lo, hi = int(train_labels.min()), int(train_labels.max())
-        if lo < 0 or hi >= num_classes:
-            raise ValueError(f"train label {lo if lo < 0 else hi} outside [0, {num_classes})")
+        if train_labels is not None:
+            if not isinstance(train_labels, torch.Tensor) or not train_labels.is_cuda:
+                raise ValueError("train_labels: expected a device tensor")
+            if train_labels.dim() != 1 or train_labels.shape[0] != f.shape[0] or train_labels.dtype not in (torch.int64, torch.int32):
+                raise ValueError("train_labels: expected one int64 / int32 label per train row")
+            if not 1 <= num_classes <= MAX_CLASSES:
+                raise ValueError(f"num_classes must be in [1, {MAX_CLASSES}]")
+            lo, hi = int(train_labels.min()), int(train_labels.max())
+            if lo < 0 or hi >= num_classes:
+                raise ValueError(f"train label {lo if lo < 0 else hi} outside [0, {num_classes})")
         self.nt, self.dim, self.num_classes = f.shape[0], f.shape[1], num_classes
-        self.labels = train_labels.to(torch.int32).contiguous()
+        self.labels = None if train_labels is None else train_labels.to(torch.int32).contiguous()
         self.train3 = torch.empty(self.nt, 3 * self.dim, dtype=torch.bfloat16, device=f.device)
         ops.split_bf16x3(f, self.train3, True)
         self._ws = None
@@ -78,6 +79,8 @@ class KnnIndex:
     def vote(self, values, indices, ks, T, return_votes=False):
         """pred i32 [m, Nq, 5] (and votes f32 [m, Nq, num_classes]) for the ascending list `ks` from one neighbour list."""
         ks = [int(k) for k in ks]
+        if self.labels is None:
+            raise ValueError("this index was built without train_labels: it serves `search` only")
         if not 1 <= len(ks) <= MAX_KS or any(b <= a for a, b in zip(ks, ks[1:])) or ks[0] < 1 or ks[-1] > values.shape[1]:
             raise ValueError(f"ks = {ks}: 1 to {MAX_KS} strictly ascending values, the largest at most {values.shape[1]}")
         if not T > 0:

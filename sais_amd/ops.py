@@ -892,3 +892,36 @@ def grad_norms(grad, chunks, nchunks, seg_first, nseg, partial, norms, scale=1.0
 
 def adamw_ema_step(desc):
     L.call("sais_adamw_ema_step", ctypes.byref(desc), _stream())
+
+
+# ---- copy detection and image retrieval (csrc/retrieval.hip)
+def vit_cls_gem_norm(x, frames, ntok, gamma, beta, eps, y, p_clamp_min=1e-6):
+    """y f32 [frames, >= 768] = [CLS | GeM(p = 4) of the patch tokens] of the final LayerNorm of x f32 [frames * ntok, 384]."""
+    _chk(x, F32, "x"); _chk(y, F32, "y")
+    L.call("sais_vit_cls_gem_norm", _p(x), ntok * 384, frames, ntok, 384, _p(gamma), _p(beta), eps, p_clamp_min, _p(y),
+           y.stride(0), _stream())
+
+
+def colmean_cov(x, mean, cov):
+    """mean f32 [D] and cov f32 [D, D] = x^T x / N (uncentred) of x f32 [N, D]; the workspace comes from the caching allocator."""
+    _chk(x, F32, "x"); _chk(mean, F32, "mean"); _chk(cov, F32, "cov")
+    N, D = x.shape
+    need = L.load().sais_colmean_cov_workspace_bytes(N, D)
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=x.device)
+    L.call("sais_colmean_cov", _p(x), x.stride(0), N, D, _p(mean), _p(cov), _p(ws), need, _stream())
+
+
+def center_rows_(x, mean):
+    _chk(x, F32, "x"); _chk(mean, F32, "mean")
+    L.call("sais_center_rows", _p(x), x.stride(0), x.shape[0], x.shape[1], _p(mean), _stream())
+
+
+def rank_positions(sim, offsets, items, pos):
+    _chk(sim, F32, "sim")
+    L.call("sais_rank_positions", _p(sim), sim.stride(0), sim.shape[0], sim.shape[1], _p(offsets), _p(items), _p(pos), _stream())
+
+
+def resize_bilinear(x, scale, y):
+    _chk(x, F32, "x"); _chk(y, F32, "y")
+    L.call("sais_resize_bilinear_f32", _p(x), x.shape[0], x.shape[2], x.shape[3], float(scale), _p(y), y.shape[2], y.shape[3],
+           _stream())

@@ -321,6 +321,27 @@ class VisionTransformer(nn.Module):
         return self._last_norms(self._check_input(x, "dense_features"), n, streaming=True)
 
     @torch.no_grad()
+    def retrieval_features(self, x, cls_only=False):
+        """The Copydays descriptor (eval_copy_detection.py:166-175), f32 [F, 768], at ANY resolution: x as dense_features takes it
+        (same checks, same errors).  Columns 0..383 are the CLS token of norm(x) after the last block, columns 384..767 the GeM
+        pooling with exponent 4 of its patch tokens clamped at 1e-6 — the reference's torch.cat(dim=1), concatenated, not
+        interleaved.  Inference only.  Launches: dense_features' for every block, then sais_vit_cls_gem_norm on the residual
+        stream: the normed [F, N, 384] tensor is never written.  cls_only: f32 [F, 384], the first half alone (what
+        eval_image_retrieval.py reads: model(x) at any resolution) — the blocks, then one sais_layernorm_fwd launch over the CLS
+        rows, which is the launch that writes the first half of the full descriptor, so the bits are the same; no GeM pass."""
+        x = self._check_input(x, "retrieval_features")
+        f, Fr = self._engine(x.device), x.shape[0]
+        xs = self._forward_kernels(x, save=False, end="blocks", streaming=True)[0]
+        ntok = xs.shape[0] // Fr
+        if cls_only:
+            feats = torch.empty(Fr, D, dtype=torch.float32, device=x.device)
+            ops.layernorm_fwd(xs, Fr, ntok * D, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6, y32=feats)
+            return feats
+        feats = torch.empty(Fr, 2 * D, dtype=torch.float32, device=x.device)
+        ops.vit_cls_gem_norm(xs, Fr, ntok, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6, feats)
+        return feats
+
+    @torch.no_grad()
     def cls_attention(self, x):
         """get_last_selfattention(x)[:, :, 0, :] (vision_transformer.py:216-223) at ANY resolution: x as dense_features takes it
         (same checks, same errors), returns f32 [F, 6, 1 + hw]: the softmax row of the CLS query of the last block over all
