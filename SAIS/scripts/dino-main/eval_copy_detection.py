@@ -9,7 +9,7 @@ without the normed token tensor, exact-f32 whitening statistics, a top-20 search
 Kept: every flag, the block order of CopydaysDataset, `Resize((imsize, imsize), bicubic)` + ImageNet normalisation (on Pillow in
 the DataLoader workers), the optional distractors and whitening sets, the printed lines ("Extraction of ... features done.
 Shape: ...", "Using distractors...", "keeping .. % of the energy", "eval on <block> mAP=..").
-Differences: only `--arch vit_small --patch_size 16` (the defaults here; anything else is refused with a message); without
+Differences: only `--arch vit_small` with `--patch_size 16` or `8` (the defaults here; anything else is refused with a message); without
 `--pretrained_weights` the weights stay random and the script says so (no download); one process (WORLD_SIZE > 1 exits, as
 eval_knn.py here); `--dist_url` / `--local_rank` / `--use_cuda` are accepted and ignored; the block sizes come from the directory
 listing (157 per block and 229 for `strong` on the real data, which the reference hard-codes), blocks that are absent are left
@@ -43,7 +43,7 @@ def get_args_parser():
     parser.add_argument('--use_cuda', default=True, type=bool_flag,
                         help="Accepted for compatibility: the features always stay on the GPU.")
     parser.add_argument('--arch', default='vit_small', type=str, help='Architecture (vit_small only)')
-    parser.add_argument('--patch_size', default=16, type=int, help='Patch resolution of the model (16 only).')
+    parser.add_argument('--patch_size', default=16, type=int, help='Patch resolution of the model (16 or 8).')
     parser.add_argument("--checkpoint_key", default="teacher", type=str,
                         help='Key to use in the checkpoint (example: "teacher")')
     parser.add_argument('--num_workers', default=10, type=int, help='Number of data loading workers per GPU.')
@@ -65,9 +65,9 @@ def main(argv=None):
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         sys.exit("eval_copy_detection.py runs as one process on one GPU: multi-rank feature extraction is not implemented "
                  "(start it without a distributed launcher)")
-    if args.arch.replace("deit", "vit") != "vit_small" or args.patch_size != 16:
+    if args.arch.replace("deit", "vit") != "vit_small" or args.patch_size not in (16, 8):
         sys.exit(f"Architecture {args.arch} / patch size {args.patch_size} not supported: this path runs --arch vit_small "
-                 "--patch_size 16 only")
+                 "--patch_size 16 or 8 only")
     print("\n".join("%s: %s" % (k, str(v)) for k, v in sorted(dict(vars(args)).items())))
     dev = torch.device("cuda:0")
     print(f"Model {args.arch} {args.patch_size}x{args.patch_size} built.")

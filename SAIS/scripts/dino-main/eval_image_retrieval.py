@@ -10,7 +10,7 @@ instead of an argsort of the whole database).
 Kept: every flag, `gnd_<dataset>.pkl`, `img.thumbnail((imsize, imsize), LANCZOS)` + ImageNet normalisation (on Pillow in the
 DataLoader workers), batch size 1 (images keep their aspect ratio, so their sizes differ), the Medium / Hard groupings, and the
 lines ">> <dataset>: mAP M: .., H: .." and ">> <dataset>: mP@k[ 1  5 10] M: .., H: ..".
-Differences: only `--arch vit_small --patch_size 16` (anything else is refused with a message); without `--pretrained_weights`
+Differences: only `--arch vit_small` with `--patch_size 16` or `8` (anything else is refused with a message); without `--pretrained_weights`
 the weights stay random and the script says so (no download of the Google-Landmarks checkpoint); one process (WORLD_SIZE > 1
 exits, as eval_knn.py here); `--dist_url` / `--local_rank` / `--use_cuda` are accepted and ignored; sides that are no multiple of
 16 are cropped at the right and bottom to the multiple below, which is what the reference's patch embedding computes; equal
@@ -38,7 +38,7 @@ def get_args_parser():
     parser.add_argument('--use_cuda', default=True, type=bool_flag,
                         help="Accepted for compatibility: the features always stay on the GPU.")
     parser.add_argument('--arch', default='vit_small', type=str, help='Architecture (vit_small only)')
-    parser.add_argument('--patch_size', default=16, type=int, help='Patch resolution of the model (16 only).')
+    parser.add_argument('--patch_size', default=16, type=int, help='Patch resolution of the model (16 or 8).')
     parser.add_argument("--checkpoint_key", default="teacher", type=str,
                         help='Key to use in the checkpoint (example: "teacher")')
     parser.add_argument('--num_workers', default=10, type=int, help='Number of data loading workers per GPU.')
@@ -53,9 +53,9 @@ def main(argv=None):
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         sys.exit("eval_image_retrieval.py runs as one process on one GPU: multi-rank feature extraction is not implemented "
                  "(start it without a distributed launcher)")
-    if args.arch.replace("deit", "vit") != "vit_small" or args.patch_size != 16:
+    if args.arch.replace("deit", "vit") != "vit_small" or args.patch_size not in (16, 8):
         sys.exit(f"Architecture {args.arch} / patch size {args.patch_size} not supported: this path runs --arch vit_small "
-                 "--patch_size 16 only")
+                 "--patch_size 16 or 8 only")
     print("\n".join("%s: %s" % (k, str(v)) for k, v in sorted(dict(vars(args)).items())))
     dev = torch.device("cuda:0")
 

@@ -9,7 +9,7 @@ memory, one search for every k of --nb_knn).
 Kept: every flag, `ImageFolder` listing rules, the eval transform (Resize 256 bicubic, CenterCrop 224, ImageNet
 normalisation; on Pillow in the DataLoader workers), `--checkpoint_key` and the `module.` / `backbone.` prefix handling,
 the four `--dump_features` / `--load_features` files, and the line "{k}-NN classifier result: Top1: .., Top5: ..".
-Differences: only `--arch vit_small --patch_size 16`; without `--pretrained_weights` the weights stay random and the
+Differences: only `--arch vit_small` with `--patch_size 16` or `8`; without `--pretrained_weights` the weights stay random and the
 script says so (no download); one process (WORLD_SIZE > 1 exits); `--dist_url` / `--local_rank` are accepted and
 ignored; a k larger than the train set is reported and skipped; any number of test rows works.
 """

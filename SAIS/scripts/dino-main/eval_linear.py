@@ -12,7 +12,7 @@ bicubic, CenterCrop 224), DistributedSampler's epoch order at world size 1, `--v
 log.txt with the keys train_loss, train_lr, epoch, test_loss, test_acc1, test_acc5 (acc5 only with --num_labels >= 5),
 checkpoint.pth.tar in the reference's layout with resume, the lines "Accuracy at epoch ...", "Max accuracy so far" and the
 final "Top-1 test accuracy".
-Differences: only `--arch vit_small --patch_size 16`.  `--lr` takes one OR SEVERAL values: the backbone pass, which
+Differences: only `--arch vit_small` with `--patch_size 16` or `8`.  `--lr` takes one OR SEVERAL values: the backbone pass, which
 dominates a step, then serves one head per value (at most 8).  One value behaves and names its files exactly as the
 reference; with several, head i is saved as checkpoint_lr<value>.pth.tar, log.txt gets one line per head and epoch with
 an extra `lr0` key (the head's --lr value) and the final line reports the best head.  One process (WORLD_SIZE > 1 exits);

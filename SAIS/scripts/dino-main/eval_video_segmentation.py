@@ -21,7 +21,7 @@ Decisions where this script differs from the reference:
   * --bs.  The reference parses it and ignores it.  Features do not depend on the propagation, so this script extracts the
     dense features of --bs frames per ViT pass and then propagates frame by frame.
   * Checkpoints.  Loaded as eval_knn.py does (sais_amd.model_io.load_dino_backbone); without --pretrained_weights the weights stay
-    random (seeded: the same in every run) and the script says so (no download).  Only --arch vit_small --patch_size 16.
+    random (seeded: the same in every run) and the script says so (no download).  Only --arch vit_small, --patch_size 16 or 8.
 """
 import argparse
 import os
@@ -67,7 +67,8 @@ def extract_features(model, frame_list, bs, dev):
         x = torch.stack([f for f, _, _ in frames]).to(dev)
         feats.append(model.dense_features(x, 1)[0][:, 1:].contiguous())
     feats = torch.cat(feats)
-    return feats, x.shape[2] // 16, x.shape[3] // 16, sizes
+    patch = model.patch_embed.patch_size
+    return feats, x.shape[2] // patch, x.shape[3] // patch, sizes
 
 
 @torch.no_grad()

@@ -24,8 +24,8 @@ Decisions where this script differs from the reference:
   * --resize is Pillow's bilinear filter on the decoded image under torchvision's size rule (one int: the short side; two:
     h w), not torchvision's antialiased tensor resize: this step is PARITY-UNPINNED.
   * Checkpoints.  Loaded as eval_knn.py does; without --pretrained_weights the weights stay random (seeded: the same in every
-    run) and the script says so.  No download.  Only --arch vit_small --patch_size 16; --patch_size defaults to 16 (the
-    reference's default, 8, is a backbone this path does not have).
+    run) and the script says so.  No download.  Only --arch vit_small with --patch_size 16 or 8; --patch_size defaults to 16 (the
+    reference's default is 8: ViT-S/8, inference only here).
 """
 import argparse
 import glob
@@ -137,7 +137,7 @@ class VideoGenerator:
                 nxt = None
             x = torch.stack(batch).to(self.dev)
             probs = self.model.cls_attention(x)
-            _, rgb = attnviz.render(probs, (x.shape[2] // 16, x.shape[3] // 16), threshold=self.args.threshold, cmap="inferno",
+            _, rgb = attnviz.render(probs, (x.shape[2] // self.args.patch_size, x.shape[3] // self.args.patch_size), threshold=self.args.threshold, cmap="inferno",
                                     patch=self.args.patch_size)
             rgb = rgb.cpu().numpy()
             for j in range(len(batch)):
@@ -149,7 +149,7 @@ def get_args_parser():
     parser = argparse.ArgumentParser("Generation self-attention video")
     parser.add_argument("--arch", default="vit_small", type=str, choices=["vit_tiny", "vit_small", "vit_base"],
                         help="backbone (this path: vit_small only)")
-    parser.add_argument("--patch_size", default=16, type=int, help="patch size of the backbone (this path: 16 only)")
+    parser.add_argument("--patch_size", default=16, type=int, help="patch size of the backbone (this path: 16 or 8)")
     parser.add_argument("--pretrained_weights", default="", type=str, help="checkpoint file of the backbone")
     parser.add_argument("--checkpoint_key", default="teacher", type=str, help="entry of the checkpoint dict that holds the weights")
     parser.add_argument("--input_path", required=True, type=str,

@@ -230,8 +230,8 @@ def main():
                          'folder is marked so that a later run with a checkpoint regenerates it)')
     ap.add_argument('--raft_iters', default=12, type=int)
     args = ap.parse_args()
-    if args.arch != 'vit_small' or args.patch_size != 16:
-        raise SystemExit('the MI355X kernels implement vit_small / patch 16 only')
+    if args.arch != 'vit_small' or args.patch_size not in (16, 8):
+        raise SystemExit('the MI355X kernels implement vit_small with patch 16 or 8 only')
     if args.segmentation or args.segmentation_to_reps:
         raise SystemExit('segmentation is out of scope of this build (SURVEY.md §2)')
     t0 = time.time()
@@ -242,12 +242,13 @@ def main():
     from sais_amd.parallel import gather_in_rank_order, init_from_env, shard_range
     rank, world, local = init_from_env()                 # torch.distributed.run: frames of a video are sharded over the ranks
     dev = torch.device('cuda', local if world > 1 else args.local_rank)
-    ckpt = args.checkpoint or os.path.join(args.data_path, 'scripts', 'dino-main', 'outputs', 'dino_deitsmall16_pretrain.pth')
+    ckpt = args.checkpoint or os.path.join(args.data_path, 'scripts', 'dino-main', 'outputs',
+                                           f'dino_deitsmall{args.patch_size}_pretrain.pth')
     if not os.path.exists(ckpt):
-        print(f'[extract] {ckpt} not found: using seeded random ViT-S/16 weights (no network in this environment)')
+        print(f'[extract] {ckpt} not found: using seeded random ViT-S/{args.patch_size} weights (no network in this environment)')
         ckpt = None
     torch.manual_seed(0)
-    vit = load_vit(ckpt, device=dev, drop_path_rate=args.drop_path_rate)
+    vit = load_vit(ckpt, device=dev, drop_path_rate=args.drop_path_rate, patch_size=args.patch_size)
     flow = args.optical_flow_to_reps
     sub = 'flows' if flow else 'images'
     videos = [args.video] if args.video else sorted(os.listdir(os.path.join(args.data_path, sub)))

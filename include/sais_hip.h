@@ -823,6 +823,20 @@ int sais_vit_attn_fwd_any(const void* qkv, long ldqkv, int frames, int ntok, voi
                           void* stream);
 int sais_patchify_rect(const float* frames_f32 /*[F,3,H,W]*/, int frames, int H, int W, void* patches_bf16, void* stream);
 
+/* ================================================================ ViT-S/8: the patch-8 backbone (inference)
+ * (sais_amd/csrc/vit8.hip, host: VisionTransformer with patch_size = 8).  Additive entries: the ABI version does not change.
+ * sais_patchify_rect8: frames f32 [F, 3, H, W], H and W positive multiples of 8 -> patches bf16 [F * (H/8) * (W/8), 192], patch
+ *   rows in row-major order of the (H/8, W/8) grid, the 192 columns in (c, py, px) order (the Conv2d weight of PatchEmbed
+ *   flattened); each value is the round-to-nearest-even bf16 of the f32 pixel.  Anything else is SAIS_ERR_ARG.
+ * sais_vit_attn_cls_fwd_any: the contract of sais_vit_attn_cls_fwd for any 2 <= ntok <= SAIS_VIT_ATTN_ANY_MAX_TOKENS.  qkv bf16
+ *   [frames * ntok, 1152] (row stride ldqkv >= 1152, a multiple of 8), out bf16 [frames, 384] (row stride ldo >= 384, a multiple
+ *   of 8): the attention output of the CLS query of every (frame, head).  q is read from the CLS row ONLY (the q columns of the
+ *   other rows may be unwritten), K and V of all tokens once; scores, row maximum and sum in fp32, P is not rounded; rows past
+ *   ntok are reached by clamped loads only.  One workgroup per (frame, head), no atomics: bit-reproducible, and a frame's result
+ *   does not depend on the number of frames in the launch.  Forward only.                                                      */
+int sais_patchify_rect8(const float* frames_f32 /*[F,3,H,W]*/, int frames, int H, int W, void* patches_bf16, void* stream);
+int sais_vit_attn_cls_fwd_any(const void* qkv, long ldqkv, int frames, int ntok, void* out, long ldo, void* stream);
+
 /* ================================================================ video object segmentation: label propagation
  * (dino-main/eval_video_segmentation.py; sais_amd/csrc/vos.hip, host: sais_amd/vos.py).
  * sais_vos_propagate: label_propagation (:113-150) for one target frame.  n = h * w <= SAIS_VOS_MAX_PATCHES patches, row-major.

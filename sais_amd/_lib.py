@@ -275,6 +275,9 @@ SIGNATURES = {
     "sais_center_rows": [c_void_p, c_long, c_long, c_int, c_void_p, c_void_p],
     "sais_rank_positions": [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "sais_resize_bilinear_f32": [c_void_p, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_int, c_int, c_void_p],
+    # ViT-S/8 (csrc/vit8.hip)
+    "sais_patchify_rect8": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
+    "sais_vit_attn_cls_fwd_any": [c_void_p, c_long, c_int, c_int, c_void_p, c_long, c_void_p],
 }
 
 _lib = None

@@ -85,9 +85,10 @@ def loadModel(rank, world_size, savepath, data_type, nclasses, domain, rep_dim, 
     return {'model': model, 'prototypes': protos}, optimizer, device
 
 
-def load_vit(path=None, device='cuda:0', drop_path_rate=0.1):
-    """extract_representations.loadModel (:181-219): vit_small(patch_size=16) + strict load of the DINO checkpoint."""
-    model = vit_small(patch_size=16, drop_path_rate=drop_path_rate)
+def load_vit(path=None, device='cuda:0', drop_path_rate=0.1, patch_size=16):
+    """extract_representations.loadModel (:181-219): vit_small(patch_size) + strict load of the DINO checkpoint (patch 16:
+    dino_deitsmall16_pretrain.pth; patch 8, inference only: dino_deitsmall8_pretrain.pth)."""
+    model = vit_small(patch_size=patch_size, drop_path_rate=drop_path_rate)
     if path is not None:
         sd = torch.load(path, map_location='cpu', weights_only=False)
         if isinstance(sd, dict) and 'student' in sd:            # surgical-DINO variant (:190-199)
@@ -109,15 +110,15 @@ def backbone_state_dict(ckpt, checkpoint_key="teacher"):
 
 def load_dino_backbone(args, dev, seed=None, freeze=False, random="random"):
     """The frozen backbone of a DINO tool from its parsed flags (--arch, --patch_size, --pretrained_weights,
-    --checkpoint_key): vit_small / 16 in eval(), with the checkpoint loaded as utils.load_pretrained_weights does, else the
+    --checkpoint_key): vit_small with 16 x 16 or 8 x 8 patches in eval(), with the checkpoint loaded as utils.load_pretrained_weights does, else the
     weights of its initialisation and a message; never a download.  seed: torch's seed before the initialisation (a backbone
     without --pretrained_weights is then the same in every invocation); freeze: no parameter requires a gradient; random:
     how the message names the weights that stay."""
-    if args.arch.replace("deit", "vit") != "vit_small" or args.patch_size != 16:
-        raise NotImplementedError("MI355X path: --arch vit_small --patch_size 16")
+    if args.arch.replace("deit", "vit") != "vit_small" or args.patch_size not in (16, 8):
+        raise NotImplementedError("MI355X path: --arch vit_small --patch_size 16 (or --patch_size 8, inference only)")
     if seed is not None:
         torch.manual_seed(seed)
-    model = vit_small(patch_size=16, num_classes=0).to(dev)
+    model = vit_small(patch_size=args.patch_size, num_classes=0).to(dev)
     if args.pretrained_weights and os.path.isfile(args.pretrained_weights):
         ckpt = torch.load(args.pretrained_weights, map_location="cpu", weights_only=False)
         if args.checkpoint_key is not None and isinstance(ckpt, dict) and args.checkpoint_key in ckpt:

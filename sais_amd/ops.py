@@ -545,6 +545,14 @@ def vit_attn_cls_fwd(qkv, frames, out_c, ntok=197):
            lambda: L.call("sais_vit_attn_cls_fwd", _p(qkv), qkv.stride(0), frames, ntok, _p(out_c), out_c.stride(0), _stream()))
 
 
+def vit_attn_cls_fwd_any(qkv, frames, ntok, out_c):
+    """sais_vit_attn_cls_fwd's contract at any 2 <= ntok <= 4097 (csrc/vit8.hip): one workgroup per (frame, head)."""
+    _chk(qkv, BF16, "qkv"); _chk(out_c, BF16, "out")
+    _timed("vit_attn_cls_fwd_any", 4.0 * frames * 6 * ntok * 64, 2 * frames * ntok * 768,
+           lambda: L.call("sais_vit_attn_cls_fwd_any", _p(qkv), qkv.stride(0), frames, ntok, _p(out_c), out_c.stride(0),
+                          _stream()))
+
+
 def vit_attn_cls_bwd(qkv, dout_c, frames, dqkv, ntok=197):
     """dqkv bf16 [frames*ntok, 1152] (written entirely) from the compact dout_c bf16 [frames, 384]."""
     _chk(qkv, BF16, "qkv"); _chk(dout_c, BF16, "dout"); _chk(dqkv, BF16, "dqkv")
@@ -643,6 +651,13 @@ def patchify_rect(frames_f32, patches):
     """frames f32 [F,3,H,W] (H, W multiples of 16) -> bf16 [F*(H/16)*(W/16), 768], patch rows in row-major grid order."""
     _chk(frames_f32, F32, "frames"); _chk(patches, BF16, "patches")
     L.call("sais_patchify_rect", _p(frames_f32), frames_f32.shape[0], frames_f32.shape[2], frames_f32.shape[3], _p(patches),
+           _stream())
+
+
+def patchify_rect8(frames_f32, patches):
+    """frames f32 [F,3,H,W] (H, W multiples of 8) -> bf16 [F*(H/8)*(W/8), 192], patch rows in row-major grid order (csrc/vit8.hip)."""
+    _chk(frames_f32, F32, "frames"); _chk(patches, BF16, "patches")
+    L.call("sais_patchify_rect8", _p(frames_f32), frames_f32.shape[0], frames_f32.shape[2], frames_f32.shape[3], _p(patches),
            _stream())
 
 

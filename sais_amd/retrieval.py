@@ -7,8 +7,8 @@ sais_probe_logits, sais_l2norm_fwd), `copy_detection_topk` (KnnIndex.search: no 
 `multi_scale` (sais_resize_bilinear_f32).  Host side, in fp64 as the reference: the eigendecomposition of the whitening matrix
 (np.linalg.eigh), both average-precision formulas, `copydays_map`, `compute_map`.  Host tensors raise: there is no CPU fallback.
 
-Frames whose sides are not multiples of 16 are cropped at the right and bottom to the multiple below (`crop_to_patches`).  That is
-exactly what the reference computes: its stride-16 convolution drops the remainder and `interpolate_pos_encoding` uses
+Frames whose sides are not multiples of the patch size (16; 8 on a ViT-S/8 backbone) are cropped at the right and bottom to the multiple below (`crop_to_patches`).  That is
+exactly what the reference computes: its strided convolution drops the remainder and `interpolate_pos_encoding` uses
 `w // patch_size`, so the pixels past the last whole patch never reach a token.
 """
 import os
@@ -45,18 +45,18 @@ def _l2norm(x, out):
 
 
 # ------------------------------------------------------------------------------------------------------------ frames
-def cropped_size(h, w):
+def cropped_size(h, w, patch=PATCH):
     """(h, w) cut down to multiples of the patch size; a side below one patch raises."""
-    if h < PATCH or w < PATCH:
-        raise ValueError(f"a {h} x {w} frame holds no whole {PATCH} x {PATCH} patch")
-    return h // PATCH * PATCH, w // PATCH * PATCH
+    if h < patch or w < patch:
+        raise ValueError(f"a {h} x {w} frame holds no whole {patch} x {patch} patch")
+    return h // patch * patch, w // patch * patch
 
 
-def crop_to_patches(x):
-    """x [F, 3, H, W] without the right and bottom remainders of H and W modulo 16 (see the module docstring)."""
+def crop_to_patches(x, patch=PATCH):
+    """x [F, 3, H, W] without the right and bottom remainders of H and W modulo the patch size (see the module docstring)."""
     if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.shape[1] != 3:
         raise ValueError("expected [F, 3, H, W]")
-    h, w = cropped_size(x.shape[2], x.shape[3])
+    h, w = cropped_size(x.shape[2], x.shape[3], patch)
     return x if (h, w) == tuple(x.shape[2:]) else x[:, :, :h, :w].contiguous()
 
 
@@ -83,12 +83,14 @@ def resize_bilinear(x, s):
 @torch.no_grad()
 def multi_scale(samples, model):
     """utils.multi_scale (utils.py:816-830): the mean of model(.) over the scales 1, 1/sqrt(2), 1/2 of `samples`, divided by the
-    norm of the WHOLE result tensor, as the reference does.  Each scale is cropped to multiples of 16 before `model` sees it.
+    norm of the WHOLE result tensor, as the reference does.  Each scale is cropped to multiples of the patch size (model.patch
+    where the callable carries it, as those of cls_features / descriptor_features do; else 16) before `model` sees it.
     model: a callable on device frames f32 [F, 3, H, W] (`cls_features(vit)` for the retrieval evaluation)."""
     if not isinstance(samples, torch.Tensor) or not samples.is_cuda:
         raise L.SaisHipError("multi_scale: expected a device tensor (no CPU fallback)")
     frames = samples.float().contiguous()
-    feats = [model(crop_to_patches(frames if s == 1 else resize_bilinear(frames, s))) for s in SCALES]
+    patch = getattr(model, "patch", PATCH)
+    feats = [model(crop_to_patches(frames if s == 1 else resize_bilinear(frames, s), patch)) for s in SCALES]
     mean = torch.stack(feats).sum(0) / len(SCALES)
     return mean / mean.norm()
 
@@ -97,12 +99,16 @@ def cls_features(vit):
     """model(x) of the reference at any resolution: the CLS token of the final norm, f32 [F, 384] (the first half of
     retrieval_features, bit for bit), of the frames cropped to whole patches.  Only the final LayerNorm of the CLS rows runs
     after the blocks: the GeM pass over the patch rows is not computed."""
-    return lambda x: vit.retrieval_features(crop_to_patches(x), cls_only=True)
+    fn = lambda x: vit.retrieval_features(crop_to_patches(x, fn.patch), cls_only=True)
+    fn.patch = vit.patch_embed.patch_size
+    return fn
 
 
 def descriptor_features(vit):
     """The Copydays descriptor f32 [F, 768] of the frames cropped to whole patches."""
-    return lambda x: vit.retrieval_features(crop_to_patches(x))
+    fn = lambda x: vit.retrieval_features(crop_to_patches(x, fn.patch))
+    fn.patch = vit.patch_embed.patch_size
+    return fn
 
 
 # ------------------------------------------------------------------------------------------------------------ whitening

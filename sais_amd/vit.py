@@ -21,6 +21,10 @@ rates linspace(0, drop_path_rate, depth); SAIS itself only ever runs the ViT in 
 only): their attention streams keys and values through LDS (csrc/attn_any.hip) instead of keeping a head resident, and
 `cls_attention` ends in the CLS row of the last block's softmax (csrc/attnviz.hip) instead of `get_last_selfattention`'s
 [F, 6, N, N] tensor, which stays a 224 x 224 / 96 x 96 call.
+`vit_small(patch_size=8)` (ViT-S/8: 8 x 8 patches, a 28 x 28 positional grid, 785 tokens at 224 x 224) is an INFERENCE backbone: every
+method takes any H x W in multiples of 8 up to 4097 tokens and runs the streaming launch list with the 8 x 8 gather (csrc/vit8.hip)
+and the patch GEMM at K = 192; forward() and probe_features() keep the CLS-only last block, whose attention beyond the 200 tokens of
+attn_cls.hip is sais_vit_attn_cls_fwd_any.  A forward that needs gradients raises: training runs on patch 16.
 """
 import math
 import os
@@ -38,6 +42,7 @@ D, NTOK, HEADS, HID, PATCH_K = 384, 197, 6, 1536, 768
 _PRUNE_Q = os.environ.get("SAIS_VIT_PRUNE_Q", "1") != "0"     # the CLS-only last block computes q for the CLS rows only
 SIDES = {224: 197, 96: 37}          # frame sizes forward() takes -> tokens (the resident attention is instantiated per count)
 MAX_DENSE_TOKENS = 4097             # dense_features: the streaming attention (sais_vit_attn_fwd_any) takes any count up to this
+CLS_WAVE_MAX_TOKENS = 200           # the one-wave CLS-query attention (attn_cls.hip); beyond it: sais_vit_attn_cls_fwd_any
 
 
 def _cubic_taps(t, A=-0.75):
@@ -95,11 +100,11 @@ class _Block(nn.Module):
 
 
 class _PatchEmbed(nn.Module):
-    def __init__(self):
+    def __init__(self, patch_size=16):
         super().__init__()
-        self.proj = nn.Conv2d(3, D, kernel_size=16, stride=16)
-        self.num_patches = 196
-        self.patch_size = 16
+        self.proj = nn.Conv2d(3, D, kernel_size=patch_size, stride=patch_size)
+        self.num_patches = (224 // patch_size) ** 2
+        self.patch_size = patch_size
 
 
 def _trunc_normal_(t, std=0.02):
@@ -111,12 +116,12 @@ def _empty(dtype, dev):
     return lambda *s: torch.empty(*s, dtype=dtype, device=dev)
 
 
-def _row_groups(imgs):
+def _row_groups(imgs, patch=16):
     """One dict per resolution group: frames, tokens, its row / patch-row / frame offset in the stacked tensors and the same
     ranges as slices (`rows`, `prows`, `frames`), the interpolation map (set by the embedding).  Returns also the three totals."""
     groups, off, poff, foff = [], 0, 0, 0
     for im in imgs:
-        Fr, ntok = im.shape[0], 1 + (im.shape[2] // 16) * (im.shape[3] // 16)
+        Fr, ntok = im.shape[0], 1 + (im.shape[2] // patch) * (im.shape[3] // patch)
         n, npat = Fr * ntok, Fr * (ntok - 1)
         groups.append(dict(Fr=Fr, ntok=ntok, off=off, poff=poff, foff=foff, interp=None, rows=slice(off, off + n),
                            prows=slice(poff, poff + npat), frames=slice(foff, foff + Fr)))
@@ -173,9 +178,14 @@ class VisionTransformer(nn.Module):
     def __init__(self, img_size=[224], patch_size=16, in_chans=3, num_classes=0, embed_dim=384, depth=12,
                  num_heads=6, mlp_ratio=4., qkv_bias=True, drop_path_rate=0., **kwargs):
         super().__init__()
-        if (patch_size, in_chans, embed_dim, num_heads, int(embed_dim * mlp_ratio), img_size[0], num_classes) != \
-                (16, 3, D, HEADS, HID, 224, 0) or not qkv_bias:
-            raise NotImplementedError("the MI355X kernels implement the ViT-S/16 @224 geometry only")
+        if (in_chans, embed_dim, num_heads, int(embed_dim * mlp_ratio), img_size[0], num_classes) != \
+                (3, D, HEADS, HID, 224, 0) or not qkv_bias or patch_size not in (16, 8):
+            raise NotImplementedError("the MI355X kernels implement the ViT-S/16 @224 geometry only (and ViT-S/8 for inference)")
+        # patch 16: training and inference.  patch 8: inference only, every method on the streaming launch list
+        self.patch = patch_size
+        self.grid0 = 224 // patch_size               # side of the positional grid: 14 or 28
+        self.ntok0 = 1 + self.grid0 ** 2             # rows of pos_embed: 197 or 785
+        self.patch_k = 3 * patch_size ** 2           # K of the patch GEMM: 768 or 192
         self.num_features = self.embed_dim = embed_dim
         self.depth = depth
         self.drop_path_rate = drop_path_rate        # identity in eval(); per-sample stochastic depth in train()
@@ -189,9 +199,9 @@ class VisionTransformer(nn.Module):
         self._bp, self._wsbuf = None, {}
         self._rng = None
         self.last_droppath_scales = None
-        self.patch_embed = _PatchEmbed()
+        self.patch_embed = _PatchEmbed(patch_size)
         self.cls_token = nn.Parameter(torch.zeros(1, 1, D))
-        self.pos_embed = nn.Parameter(torch.zeros(1, NTOK, D))
+        self.pos_embed = nn.Parameter(torch.zeros(1, self.ntok0, D))
         self.blocks = nn.ModuleList([_Block() for _ in range(depth)])
         self.norm = nn.LayerNorm(D, eps=1e-6)
         self.head = nn.Identity()
@@ -206,7 +216,7 @@ class VisionTransformer(nn.Module):
                 nn.init.constant_(m.weight, 1.0)
         self.flat = None
         self._anchor = None
-        self._interp = {}                            # (H, W) -> device f32 [ntok - 1, 196] bicubic map
+        self._interp = {}                            # (H, W) -> device f32 [ntok - 1, grid0^2] bicubic map
         self.grad_ready_hook = None                  # callable(lo, hi): flat-grad slice [lo,hi) is final
         self._t_names = [f"blocks.{i}.{n}.weight" for i in range(depth) for n in ("attn.qkv", "attn.proj", "mlp.fc1", "mlp.fc2")]
 
@@ -237,14 +247,24 @@ class VisionTransformer(nn.Module):
 
     # ------------------------------------------------------------------ public API (reference signatures)
     def forward(self, x):
-        x = self._check_input(x)
         need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in (self.cls_token, self.norm.weight))
+        if self.patch == 8:
+            if need_grad:
+                raise NotImplementedError("the patch-8 backbone is inference only (call it under torch.no_grad() or freeze its "
+                                          "parameters): training runs on patch 16")
+            x = self._check_input(x, "forward")
+            self._engine(x.device)
+            return self._forward_kernels(x, save=False, streaming=True)[0]
+        x = self._check_input(x)
         self._engine(x.device)
         if need_grad:
             return _ViTFn.apply(self, x, self._anchor)
         return self._forward_kernels(x, save=False)[0]
 
     def get_last_selfattention(self, x):
+        if self.patch == 8:
+            raise NotImplementedError("get_last_selfattention (the [F, 6, N, N] tensor) is a patch-16 call at 224 x 224 / 96 x 96; "
+                                      "cls_attention returns its CLS row at any size")
         x = self._check_input(x)
         self._engine(x.device)
         return self._forward_kernels(x, save=False, end="probs")[0]
@@ -270,6 +290,8 @@ class VisionTransformer(nn.Module):
         """vision_transformer.py:225-233: norm(x) after each of the last n blocks, oldest first, as n tensors f32
         [F, 197, 384].  Inference only (runs under no_grad, nothing is saved for a backward); 224 x 224 frames only.  Every row
         of the last block is computed (no CLS-only tail)."""
+        if self.patch == 8:                          # any size, as dense_features
+            return self._last_norms(self._check_input(x, "get_intermediate_layers"), n, streaming=True)
         x = self._check_input(x)
         if x.shape[-1] != 224:
             raise ValueError("get_intermediate_layers takes 224 x 224 frames")
@@ -286,27 +308,29 @@ class VisionTransformer(nn.Module):
         if avgpool and n != 1:
             raise ValueError("avgpool_patchtokens needs n_last_blocks = 1: the reference's torch.cat (eval_linear.py:169) "
                              f"cannot join [F, {D * n}, 1] with [F, {D}, 1]")
-        x = self._check_input(x)
-        if x.shape[-1] != 224:
+        streaming = self.patch == 8                  # patch 8: any size, the streaming launch list
+        x = self._check_input(x, "probe_features" if streaming else None)
+        if not streaming and x.shape[-1] != 224:
             raise ValueError("probe_features takes 224 x 224 frames")
         if not 1 <= n <= self.depth:
             raise ValueError(f"n = {n} must be in [1, {self.depth}]")
         f, Fr = self._engine(x.device), x.shape[0]
+        ntok = 1 + (x.shape[2] // self.patch) * (x.shape[3] // self.patch)
         if avgpool:
-            xs = self._forward_kernels(x, save=False, end="blocks")[0]
+            xs = self._forward_kernels(x, save=False, end="blocks", streaming=streaming)[0]
             feats = torch.empty(Fr, 2 * D, dtype=torch.float32, device=x.device)
-            ops.vit_cls_avgpool_norm(xs, Fr, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6, feats)
+            ops.vit_cls_avgpool_norm(xs, Fr, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6, feats, ntok=ntok)
             return feats
         if n == 1:
-            return self._forward_kernels(x, save=False)[0]
+            return self._forward_kernels(x, save=False, streaming=streaming)[0]
         feats = torch.empty(Fr, D * n, dtype=torch.float32, device=x.device)
         first = self.depth - n
 
         def tap(i, xs):            # slots of the earlier blocks; the last slot is written by the pass itself (reps_out)
             if first <= i < self.depth - 1:
-                ops.layernorm_fwd(xs, Fr, NTOK * D, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6,
+                ops.layernorm_fwd(xs, Fr, ntok * D, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6,
                                   y32=feats[:, (i - first) * D:], ldy32=D * n)
-        self._forward_kernels(x, save=False, tap=tap, reps_out=feats[:, (n - 1) * D:])
+        self._forward_kernels(x, save=False, tap=tap, reps_out=feats[:, (n - 1) * D:], streaming=streaming)
         return feats
 
     @torch.no_grad()
@@ -364,10 +388,10 @@ class VisionTransformer(nn.Module):
         ops.vit_cls_probs(q, k, Fr, ntok, probs)
         return probs
 
-    @staticmethod
-    def _check_input(x, any_size=None):
+    def _check_input(self, x, any_size=None):
         """forward()'s input as a contiguous f32 tensor.  any_size: the name of the caller that takes every H x W in multiples of
-        16 (dense_features, cls_attention) instead of the square sides of SIDES."""
+        the patch size (dense_features, cls_attention; every method of a patch-8 model) instead of the square sides of SIDES."""
+        P = self.patch
         if any_size is None:
             if not x.is_cuda:
                 raise L.SaisHipError("VisionTransformer.forward needs a device tensor: the HIP path has no CPU fallback")
@@ -376,23 +400,24 @@ class VisionTransformer(nn.Module):
             return x.contiguous().float()
         if not isinstance(x, torch.Tensor) or not x.is_cuda:
             raise L.SaisHipError(f"VisionTransformer.{any_size} needs a device tensor: the HIP path has no CPU fallback")
-        if x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1 or x.shape[2] < 16 or x.shape[3] < 16 or x.shape[2] % 16 or x.shape[3] % 16:
-            raise ValueError(f"expected [F,3,H,W] with H and W positive multiples of 16, got {tuple(x.shape)}")
+        if x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1 or x.shape[2] < P or x.shape[3] < P or x.shape[2] % P or x.shape[3] % P:
+            raise ValueError(f"expected [F,3,H,W] with H and W positive multiples of {P}, got {tuple(x.shape)}")
         H, W = x.shape[2], x.shape[3]
-        ntok = 1 + (H // 16) * (W // 16)
+        ntok = 1 + (H // P) * (W // P)
         if ntok > MAX_DENSE_TOKENS:
             raise ValueError(f"{H} x {W} frames are {ntok} tokens; at most {MAX_DENSE_TOKENS}")
         return x.contiguous().float()
 
     def _pos_table(self, H, W, dev):
-        """(positional table f32 [1 + (H/16)(W/16), 384], interpolation map or None) for H x W frames; the bicubic map is cached
-        per (H, W)."""
-        pos = self.flat.w32("pos_embed").view(NTOK, D)
+        """(positional table f32 [1 + (H/P)(W/P), 384], interpolation map or None) for H x W frames; the bicubic map is cached
+        per (H, W).  The table is the parameter itself only at 224 x 224 (:177-178: as many patches AND a square frame — a
+        448 x 112 frame at patch 8 has 784 patches and is interpolated)."""
+        pos = self.flat.w32("pos_embed").view(self.ntok0, D)
         if H == W == 224:
             return pos, None
         Wm = self._interp.get((H, W))
         if Wm is None or Wm.device != dev:
-            Wm = torch.from_numpy(pos_interp_matrix(14, H, W).astype(np.float32)).to(dev)
+            Wm = torch.from_numpy(pos_interp_matrix(self.grid0, H, W, patch=self.patch).astype(np.float32)).to(dev)
             self._interp[(H, W)] = Wm
         out = torch.empty(1 + Wm.shape[0], D, dtype=torch.float32, device=dev)
         ops.pos_interp_fwd(Wm, pos, out)
@@ -414,7 +439,7 @@ class VisionTransformer(nn.Module):
         f = self.flat
         imgs = list(img) if isinstance(img, (list, tuple)) else [img]
         dev = imgs[0].device
-        groups, M, NP, Ftot = _row_groups(imgs)
+        groups, M, NP, Ftot = _row_groups(imgs, self.patch)
         if end == "probs" and len(groups) > 1:
             raise ValueError("get_last_selfattention takes one resolution")
         # Every decision of the pass, taken once; inside the loop only "is this the last block" is left.
@@ -497,17 +522,19 @@ class VisionTransformer(nn.Module):
         return reps, saved
 
     def _embed_fwd(self, pl, imgs):
-        """Patchify, patch GEMM (+ bias + positional table) and CLS rows per group -> (patches bf16 [NP, 768], x f32 [M, 384])."""
-        f = self.flat
-        patches = pl.e16(pl.NP, PATCH_K)
+        """Patchify, patch GEMM (+ bias + positional table) and CLS rows per group -> (patches bf16 [NP, 768], x f32 [M, 384]);
+        a patch-8 model (streaming only): the 8 x 8 gather and K = 192."""
+        f, K = self.flat, self.patch_k
+        gather = ops.patchify_rect8 if self.patch == 8 else ops.patchify_rect if pl.streaming else ops.patchify
+        patches = pl.e16(pl.NP, K)
         x = pl.e32(pl.M, D)
         for im, g in zip(imgs, pl.groups):
             Fr, ntok = g["Fr"], g["ntok"]
             pg = patches[g["prows"]]
             xg = x[g["rows"]].view(Fr, ntok, D)
-            (ops.patchify_rect if pl.streaming else ops.patchify)(im, pg)
+            gather(im, pg)
             pos, g["interp"] = self._pos_table(im.shape[2], im.shape[3], pl.dev)
-            ops.gemm_nt(pg, f.w("patch_embed.proj.weight").view(D, PATCH_K), L.EPI_PATCH_F32, xg,
+            ops.gemm_nt(pg, f.w("patch_embed.proj.weight").view(D, K), L.EPI_PATCH_F32, xg,
                         bias=f.w32("patch_embed.proj.bias"), aux=pos, grp=(ntok - 1, ntok, 1))
             ops.vit_cls_rows(f.w32("cls_token"), pos, xg, Fr, ntok)
         return patches, x
@@ -607,13 +634,17 @@ class VisionTransformer(nn.Module):
 
     def _cls_tail_fwd(self, pl, i, x, ln1, qkv):
         """The last block from its qkv on, restricted to what forward() returns (the CLS rows): attention for the CLS query
-        (sais_vit_attn_cls_fwd, one launch per resolution group), then proj + residual, norm2, fc1 + GELU, fc2 + residual and
+        (sais_vit_attn_cls_fwd, one launch per resolution group; sais_vit_attn_cls_fwd_any for a token count its one wave per
+        (frame, head) cannot hold: more than CLS_WAVE_MAX_TOKENS, a patch-8 model at 224 x 224), then proj + residual, norm2, fc1 + GELU, fc2 + residual and
         the final norm on [frames, 384] tensors (all groups together).  The residual input is the strided view x[::ntok]."""
         f, p = self.flat, f"blocks.{i}."
         groups, Ftot, dp, save, e16, e32 = pl.groups, pl.Ftot, pl.dp, pl.save, pl.e16, pl.e32
         ao = e16(Ftot, D)
         for g in groups:
-            ops.vit_attn_cls_fwd(qkv[g["rows"]], g["Fr"], ao[g["frames"]], g["ntok"])
+            if g["ntok"] > CLS_WAVE_MAX_TOKENS:
+                ops.vit_attn_cls_fwd_any(qkv[g["rows"]], g["Fr"], g["ntok"], ao[g["frames"]])
+            else:
+                ops.vit_attn_cls_fwd(qkv[g["rows"]], g["Fr"], ao[g["frames"]], g["ntok"])
         cls_rows = lambda t, w: [t[g["rows"]].view(g["Fr"], g["ntok"], *w)[:, 0] for g in groups]
         one = len(groups) == 1
         x_cls = cls_rows(x, (D,))[0] if one else torch.cat(cls_rows(x, (D,)))
