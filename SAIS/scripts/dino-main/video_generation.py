@@ -17,8 +17,9 @@ Decisions where this script differs from the reference:
     --video_only has nothing it can do).  With it, frame extraction and the video.<fmt> assembly are the reference's.
   * --bs (new): frames per ViT pass.  Consecutive frames of equal size share a pass; the reference runs one frame at a time.
   * Arithmetic.  The attention is the CLS row only (no [6, N, N] tensor); mass threshold, head mean, normalisation, colormap and
-    nearest upsampling run on the device, and the JPEG is written by Pillow with the keywords plt.imsave passes on: given the
-    same attention the file is the reference's byte for byte (tests/test_attnviz_gpu.py).  matplotlib is optional (the `inferno`
+    nearest upsampling run on the device, and so does the JPEG encode (sais_amd.jpeg_enc: the file Pillow writes with the
+    keywords plt.imsave passes on, one batch per call): given the same attention the file is the reference's byte for byte
+    (tests/test_attnviz_gpu.py, tests/test_jpeg_enc_gpu.py).  matplotlib is optional (the `inferno`
     table is bundled).  Equal attention values are ordered by index (the stable rule); the reference's torch.sort leaves that
     order unspecified.
   * --resize is Pillow's bilinear filter on the decoded image under torchvision's size rule (one int: the short side; two:
@@ -139,9 +140,7 @@ class VideoGenerator:
             probs = self.model.cls_attention(x)
             _, rgb = attnviz.render(probs, (x.shape[2] // self.args.patch_size, x.shape[3] // self.args.patch_size), threshold=self.args.threshold, cmap="inferno",
                                     patch=self.args.patch_size)
-            rgb = rgb.cpu().numpy()
-            for j in range(len(batch)):
-                attnviz.save_jpeg(os.path.join(out, "attn-" + os.path.basename(paths[i + j])), rgb[j])
+            attnviz.save_jpegs([os.path.join(out, "attn-" + os.path.basename(paths[i + j])) for j in range(len(batch))], rgb)
             i += len(batch)
 
 

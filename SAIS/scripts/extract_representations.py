@@ -117,7 +117,9 @@ def extract_flows(args, t0):
             return False                             # junk of a smoke run: regenerate with the real weights
         return have >= want and info.get('count') == want
 
-    from sais_amd.raft import flow_image_uint8, flow_to_rgb
+    from sais_amd.jpeg_enc import JpegEncoder
+    from sais_amd.raft import flow_image_uint8_device, flow_to_rgb
+    encoder = JpegEncoder(dev)
     for dataset in args.data_list:
         jump = 30 if dataset in ('VUA_Lab', 'DVC_UCL') else 15                       # :488-493
         with open(os.path.join(args.data_path, 'paths', '%s_FlowPaths.csv' % dataset)) as fh:
@@ -181,11 +183,13 @@ def extract_flows(args, t0):
                 i1 = torch.stack([pairs[k][0] for k in idx]).to(dev)
                 i2 = torch.stack([pairs[k][1] for k in idx]).to(dev)
                 flows = model(i1, i2)
-                for k, fl in zip(idx, flows):
-                    img = Image.fromarray(flow_image_uint8(flow_to_rgb(fl)))          # :245-249
+                imgs = torch.stack([flow_image_uint8_device(flow_to_rgb(fl)) for fl in flows])        # :245-249
+                # Image.save's defaults (quality 75, 4:2:0, no dpi), encoded on the device: the reference's bytes (:254-262)
+                for k, blob in zip(idx, encoder.encode(imgs)):
                     out = os.path.join(args.data_path, 'flows', chunk[k]['label'])
                     os.makedirs(out, exist_ok=True)
-                    img.save(os.path.join(out, 'flows_%08d.jpg' % nflows[k]))         # :254-262
+                    with open(os.path.join(out, 'flows_%08d.jpg' % nflows[k]), 'wb') as fh:
+                        fh.write(blob)
                     saved.setdefault(chunk[k]['label'], set()).add(nflows[k])
                     nsaved += 1
         for lab in set(want) - done:                 # complete only when every distinct flow number of the video was written

@@ -532,6 +532,25 @@ int    sais_jpeg_decode(const SaisJpegBatch* batch, const unsigned char* data, c
                         void* workspace, size_t workspace_bytes, unsigned char* out /* [n,H,W,3] */, int* status,
                         void* stream);
 
+/* ---------------------------------------------------------------- JPEG encode (uint8 RGB on the device -> scan bytes)
+ * The counterpart of the decoder for images made on the device (attention heat maps, colour-coded flow): baseline sequential,
+ * 8 bit, one interleaved scan without restart markers, the four Annex K Huffman tables, YCbCr 4:2:0 (subsampling 2) or 4:4:4
+ * (subsampling 0), byte-identical to libjpeg-turbo at Pillow's defaults (rgb_ycc_convert, h2v2_downsample, jfdctint.c).
+ * sais_jpeg_encode writes, for image i, the bytes from the first entropy-coded byte through the EOI marker to
+ * out[i * out_stride ...] and their count to nbytes[i]; an image whose bytes do not fit out_stride gets nbytes[i] = -1 and
+ * nothing is written to its slot.  The headers are the caller's (sais_amd/jpeg_enc.py: header).  sais_jpeg_encode_bound (a
+ * host function) is the worst case of one image: blocks x the longest block code, doubled for byte stuffing, + padding + EOI.
+ * SAIS_ERR_ARG: n outside 1..65535, a side outside 1..65535, another subsampling, a q entry of 0 or above 255, a workspace
+ * smaller than sais_jpeg_encode_workspace_bytes, out_stride < 2. */
+typedef struct SaisJpegEncParams {
+    unsigned short q[2][64];         /* luma and chroma quantisation tables, natural order                   */
+    int subsampling;                 /* 0 = 4:4:4, 2 = 4:2:0                                                  */
+} SaisJpegEncParams;
+size_t sais_jpeg_encode_bound(int height, int width, int subsampling);
+size_t sais_jpeg_encode_workspace_bytes(int n, int height, int width, int subsampling);
+int    sais_jpeg_encode(const unsigned char* rgb, int n, int height, int width, const SaisJpegEncParams* p, void* workspace,
+                        size_t workspace_bytes, unsigned char* out, size_t out_stride, int* nbytes, void* stream);
+
 /* ---------------------------------------------------------------- DINO multi-crop augmentation (uint8 frames -> views)
  * DataAugmentationDINO, dino-main/main_dino.py:633-679, on the frames SurgDataset.__getitem__ border-crops (:295-316):
  * per view RandomResizedCrop (BICUBIC) -> flip -> ColorJitter -> grayscale -> GaussianBlur -> solarize -> ToTensor ->

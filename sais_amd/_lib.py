@@ -190,6 +190,10 @@ SIGNATURES = {
     "sais_jpeg_parse": [c_void_p, ctypes.c_size_t, c_void_p],
     "sais_jpeg_workspace_bytes": [c_int, c_int, c_int, ctypes.c_int64, c_int],
     "sais_jpeg_decode": [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p],
+    "sais_jpeg_encode_bound": [c_int, c_int, c_int],
+    "sais_jpeg_encode_workspace_bytes": [c_int, c_int, c_int, c_int],
+    "sais_jpeg_encode": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t, c_void_p,
+                         c_void_p],
     "sais_augment_workspace_bytes": [c_void_p, c_int],
     "sais_augment_crop_resize": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                  ctypes.c_size_t, c_void_p],
@@ -304,6 +308,8 @@ def load():
     lib.sais_preprocess_plan_destroy.restype = None
     lib.sais_workspace_bytes.restype = ctypes.c_size_t
     lib.sais_jpeg_workspace_bytes.restype = ctypes.c_size_t
+    lib.sais_jpeg_encode_bound.restype = ctypes.c_size_t
+    lib.sais_jpeg_encode_workspace_bytes.restype = ctypes.c_size_t
     lib.sais_augment_workspace_bytes.restype = ctypes.c_size_t
     lib.sais_gemm_tn_grouped_slab_bytes.restype = ctypes.c_size_t
     lib.sais_knn_workspace_bytes.restype = ctypes.c_size_t

@@ -5,7 +5,7 @@
 loop, `render` their tail (:207-241) — the masked head mean, min / max normalisation, the colormap and the nearest x patch
 upsampling — as one heat map at patch resolution and one colour image per frame.  There is no CPU fallback: host tensors raise.
 The image writers (`save_jpeg`, `save_png`: Pillow with the keywords plt.imsave passes on, so the files equal plt.imsave's byte
-for byte) and the frame loading of the two command-line scripts live here too; matplotlib is optional.
+for byte; `save_jpegs`: the same JPEG files for a batch on the device, encoded there by sais_amd.jpeg_enc) and the frame loading of the two command-line scripts live here too; matplotlib is optional.
 """
 import numpy as np
 import torch
@@ -16,6 +16,7 @@ from .model_io import load_dino_backbone
 MAX_N, RENDER_WS_FLOATS = 4096, 32                  # SAIS_ATTN_MASK_MAX_N, SAIS_ATTN_RENDER_WS_FLOATS
 MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)      # video_generation.py:163-165, visualize_attention.py:168
 _LUTS = {}
+_ENCODERS = {}                                     # device -> JpegEncoder (save_jpegs)
 
 
 def _probs(probs):
@@ -134,6 +135,22 @@ def save_jpeg(fname, rgb):
     its opaque RGBA image on an RGB background and saves with format='jpeg', dpi=(100, 100) (matplotlib.image.imsave)."""
     Image, a = _image(rgb)
     Image.fromarray(a).save(fname, format="jpeg", dpi=(100, 100))
+
+
+def save_jpegs(fnames, rgb):
+    """save_jpeg for a batch that is on the device: rgb u8 [F, H, W, 3] is encoded there (sais_amd.jpeg_enc) and fnames[j] gets
+    the file save_jpeg(fnames[j], rgb[j]) writes, byte for byte."""
+    if not isinstance(rgb, torch.Tensor) or not rgb.is_cuda:
+        raise ValueError("rgb: expected a device tensor (save_jpeg writes a host array)")
+    fnames = list(fnames)
+    if rgb.dim() != 4 or rgb.shape[0] != len(fnames):
+        raise ValueError(f"{len(fnames)} file names for images of shape {tuple(rgb.shape)}")
+    if rgb.device not in _ENCODERS:
+        from .jpeg_enc import JpegEncoder
+        _ENCODERS[rgb.device] = JpegEncoder(rgb.device)
+    for fname, blob in zip(fnames, _ENCODERS[rgb.device].encode(rgb.contiguous(), dpi=(100, 100))):
+        with open(fname, "wb") as fh:
+            fh.write(blob)
 
 
 def save_png(fname, rgb):

@@ -235,3 +235,9 @@ def flow_to_rgb(flow, flow_max_radius=None):
 def flow_image_uint8(rgb):
     """HWC uint8 image as the reference writes it: np.uint8(flow_rgb * 255) (extract_representations.py:245-249)."""
     return (rgb.permute(1, 2, 0) * 255).to(torch.uint8).cpu().numpy()
+
+
+def flow_image_uint8_device(rgb):
+    """flow_image_uint8 without the copy to the host: the same values as a contiguous u8 [H, W, 3] tensor on rgb's device (the
+    input of sais_amd.jpeg_enc.JpegEncoder)."""
+    return (rgb.permute(1, 2, 0) * 255).to(torch.uint8).contiguous()

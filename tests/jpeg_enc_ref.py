@@ -1,0 +1,231 @@
+"""numpy model of the baseline JPEG encoder of csrc/jpeg_enc.hip: libjpeg's colour conversion, h2v2 downsampling, jfdctint.c forward
+DCT, quantisation and Huffman coding at Pillow's defaults, restated rule by rule.  encode_scan returns the bytes from the first
+entropy-coded byte through EOI and the statistics the host test uses to show that its matrix reaches the hard cases."""
+import numpy as np
+
+from sais_amd.jpeg_enc import HUFFMAN, ZIGZAG, quant_tables
+
+F = dict(c0_298=2446, c0_390=3196, c0_541=4433, c0_765=6270, c0_899=7373, c1_175=9633, c1_501=12299, c1_847=15137, c1_961=16069,
+         c2_053=16819, c2_562=20995, c3_072=25172)
+
+
+def _codes(counts, symbols):
+    code, k, out = 0, 0, {}
+    for length in range(1, 17):
+        for _ in range(counts[length - 1]):
+            out[symbols[k]] = (code, length)
+            code += 1
+            k += 1
+        code <<= 1
+    return out
+
+
+def huffman_tables():
+    """[(code u32 [256], length u8 [256])] for DC0, AC0, DC1, AC1; length 0 = no such symbol."""
+    tabs = []
+    for _, counts, symbols in HUFFMAN:
+        code, length = np.zeros(256, np.int64), np.zeros(256, np.int64)
+        for s, (c, n) in _codes(counts, symbols).items():
+            code[s], length[s] = c, n
+        tabs.append((code, length))
+    return tabs
+
+
+def _descale(x, n):
+    return (x + (1 << (n - 1))) >> n
+
+
+def _fdct_1d(d, first):
+    """jfdctint.c, one pass over the last axis of d (int64 [..., 8])."""
+    d0, d1, d2, d3, d4, d5, d6, d7 = (d[..., i] for i in range(8))
+    t0, t7, t1, t6, t2, t5, t3, t4 = d0 + d7, d0 - d7, d1 + d6, d1 - d6, d2 + d5, d2 - d5, d3 + d4, d3 - d4
+    t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
+    n = 11 if first else 15
+    o = [None] * 8
+    if first:
+        o[0], o[4] = (t10 + t11) << 2, (t10 - t11) << 2
+    else:
+        o[0], o[4] = _descale(t10 + t11, 2), _descale(t10 - t11, 2)
+    z1 = (t12 + t13) * F["c0_541"]
+    o[2] = _descale(z1 + t13 * F["c0_765"], n)
+    o[6] = _descale(z1 - t12 * F["c1_847"], n)
+    z1, z2, z3, z4 = t4 + t7, t5 + t6, t4 + t6, t5 + t7
+    z5 = (z3 + z4) * F["c1_175"]
+    t4, t5, t6, t7 = t4 * F["c0_298"], t5 * F["c2_053"], t6 * F["c3_072"], t7 * F["c1_501"]
+    z1, z2, z3, z4 = -z1 * F["c0_899"], -z2 * F["c2_562"], -z3 * F["c1_961"] + z5, -z4 * F["c0_390"] + z5
+    o[7], o[5], o[3], o[1] = _descale(t4 + z1 + z3, n), _descale(t5 + z2 + z4, n), _descale(t6 + z2 + z3, n), _descale(t7 + z1 + z4, n)
+    return np.stack(o, axis=-1)
+
+
+def fdct_quant(plane, q):
+    """plane int64 [8 hb, 8 wb] -> quantised coefficients int64 [hb, wb, 64] in zigzag order."""
+    hb, wb = plane.shape[0] // 8, plane.shape[1] // 8
+    b = plane.reshape(hb, 8, wb, 8).transpose(0, 2, 1, 3) - 128
+    b = _fdct_1d(b, True)                                             # rows
+    b = _fdct_1d(b.transpose(0, 1, 3, 2), False).transpose(0, 1, 3, 2)  # columns
+    v = b.reshape(hb, wb, 64)
+    qv = q.astype(np.int64) << 3
+    c = np.sign(v) * ((np.abs(v) + (qv >> 1)) // qv)
+    return c[:, :, list(ZIGZAG)]
+
+
+def _pad_edge(p, rows, cols):
+    return np.pad(p, ((0, rows - p.shape[0]), (0, cols - p.shape[1])), mode="edge")
+
+
+def planes(rgb, sub):
+    """u8 [H, W, 3] -> the three padded component planes (int64), each a whole number of 8 x 8 blocks."""
+    r, g, b = (rgb[..., i].astype(np.int64) for i in range(3))
+    y = (19595 * r + 38470 * g + 7471 * b + 32768) >> 16
+    cb = (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16
+    cr = (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16
+    H, W = y.shape
+    wb, hb = -(-W // 8), -(-H // 8)
+    out = [_pad_edge(y, 8 * hb, 8 * wb)]
+    for c in (cb, cr):
+        if sub == 0:
+            out.append(_pad_edge(c, 8 * hb, 8 * wb))
+            continue
+        cw, ch = -(-W // 2), -(-H // 2)
+        cwb, chb = -(-cw // 8), -(-ch // 8)
+        p = _pad_edge(c, 2 * ch, 16 * cwb)
+        bias = np.where(np.arange(8 * cwb) % 2 == 0, 1, 2)
+        d = (p[0::2, 0::2] + p[0::2, 1::2] + p[1::2, 0::2] + p[1::2, 1::2] + bias) >> 2
+        out.append(_pad_edge(d, 8 * chb, 8 * cwb))                  # rows past ch - 1 repeat the DOWNSAMPLED row ch - 1
+    return out
+
+
+def scan_blocks(rgb, quality, sub):
+    """-> (coef int64 [NB, 64] in scan order, zigzag; comp [NB]; dummy bool [NB]; edge [NB]: 1 right, 2 bottom, 3 both)."""
+    q = quant_tables(quality)
+    H, W = rgb.shape[:2]
+    pl = planes(rgb, sub)
+    co = [fdct_quant(p, q[0 if i == 0 else 1]) for i, p in enumerate(pl)]
+    m = 16 if sub == 2 else 8
+    mx, my = -(-W // m), -(-H // m)
+    slots = [(0, 0, 0), (0, 0, 1), (0, 1, 0), (0, 1, 1), (1, 0, 0), (2, 0, 0)] if sub == 2 else [(0, 0, 0), (1, 0, 0), (2, 0, 0)]
+    nb = mx * my * len(slots)
+    coef, comp = np.zeros((nb, 64), np.int64), np.zeros(nb, np.int64)
+    dummy, edge = np.zeros(nb, bool), np.zeros(nb, np.int64)
+    mcu_y, mcu_x = np.divmod(np.arange(mx * my), mx)
+    for s, (c, dy, dx) in enumerate(slots):
+        f = 2 if (sub == 2 and c == 0) else 1
+        by, bx = f * mcu_y + dy, f * mcu_x + dx
+        hb, wb = co[c].shape[:2]
+        real = (by < hb) & (bx < wb)
+        idx = np.arange(mx * my) * len(slots) + s
+        coef[idx[real]] = co[c][by[real], bx[real]]
+        comp[idx], dummy[idx] = c, ~real
+        edge[idx] = (bx >= wb) * 1 + (by >= hb) * 2
+    return coef, comp, dummy, edge
+
+
+def encode_scan(rgb, quality=75, sub=2):
+    """u8 [H, W, 3] -> (bytes of the scan + EOI, statistics)."""
+    coef, comp, dummy, edge = scan_blocks(np.asarray(rgb), quality, sub)
+    nb = coef.shape[0]
+    tabs = huffman_tables()
+    diff = np.zeros(nb, np.int64)
+    for c in range(3):
+        real = np.flatnonzero((comp == c) & ~dummy)
+        dc = coef[real, 0]
+        diff[real] = dc - np.concatenate([[0], dc[:-1]])            # a dummy block keeps diff 0 and leaves the predictor alone
+    tsel = (comp > 0).astype(np.int64)
+
+    def size_of(v):
+        a = np.abs(v)
+        return np.where(a > 0, np.floor(np.log2(np.maximum(a, 1))).astype(np.int64) + 1, 0)
+
+    def value_bits(v, n):
+        return np.where(v >= 0, v, v - 1) & ((1 << n) - 1)
+
+    keys, bits, lens = [], [], []
+    # DC
+    n = size_of(diff)
+    dcc = np.stack([tabs[0][0], tabs[2][0]])[tsel, n]
+    dcl = np.stack([tabs[0][1], tabs[2][1]])[tsel, n]
+    keys.append(np.arange(nb) * 1024)
+    bits.append((dcc << n) | value_bits(diff, n))
+    lens.append(dcl + n)
+    # AC
+    acc, acl = np.stack([tabs[1][0], tabs[3][0]]), np.stack([tabs[1][1], tabs[3][1]])
+    ac = coef[:, 1:].copy()
+    ac[dummy] = 0
+    blk, k = np.nonzero(ac)
+    k = k + 1
+    v = ac[blk, k - 1]
+    prev = np.where(np.concatenate([[False], blk[1:] == blk[:-1]]), np.concatenate([[0], k[:-1]]), 0)
+    run = k - prev - 1
+    n = size_of(v)
+    sym = ((run & 15) << 4) | n
+    t = tsel[blk]
+    assert (acl[t, sym] > 0).all(), "an AC symbol outside the baseline tables"
+    keys.append(blk * 1024 + k * 8 + 4)
+    bits.append((acc[t, sym] << n) | value_bits(v, n))
+    lens.append(acl[t, sym] + n)
+    nzrl = run >> 4
+    for j in range(1, 4):
+        m = nzrl >= j
+        keys.append(blk[m] * 1024 + k[m] * 8 + j - 1)
+        bits.append(acc[t[m], 0xF0])
+        lens.append(acl[t[m], 0xF0])
+    eob = np.flatnonzero(ac[:, 62] == 0)
+    keys.append(eob * 1024 + 64 * 8)
+    bits.append(acc[tsel[eob], 0])
+    lens.append(acl[tsel[eob], 0])
+    keys, bits, lens = np.concatenate(keys), np.concatenate(bits), np.concatenate(lens)
+    order = np.argsort(keys, kind="stable")
+    bits, lens = bits[order], lens[order]
+    # MSB-first bit string
+    table = (bits[:, None] >> np.arange(31, -1, -1)[None, :]) & 1
+    keep = np.arange(32)[None, :] >= (32 - lens)[:, None]
+    stream = table[keep].astype(np.uint8)
+    pad = (-len(stream)) % 8
+    stream = np.concatenate([stream, np.ones(pad, np.uint8)])
+    raw = np.packbits(stream)
+    ff = raw == 0xFF
+    out = np.zeros(len(raw) + int(ff.sum()), np.uint8)
+    out[np.arange(len(raw)) + np.concatenate([[0], np.cumsum(ff)[:-1]])] = raw
+    stats = {
+        "zrl": int(nzrl.sum()), "longest_run": int(run.max()) if len(run) else 0, "stuffed": int(ff.sum()),
+        "dc_cat": int(size_of(diff).max()), "ac_cat": int(n.max()) if len(n) else 0,
+        "dummy_right": int((edge == 1).sum()), "dummy_bottom": int((edge == 2).sum()), "dummy_both": int((edge == 3).sum()),
+        "pad_bits": int(pad), "blocks": int(nb),
+    }
+    return out.tobytes() + b"\xff\xd9", stats
+
+
+# ---- the test matrix shared by tests/test_jpeg_enc_host.py and tests/test_jpeg_enc_gpu.py ------------------------------------
+GEOMETRIES = ((1, 1), (2, 2), (8, 8), (16, 16), (17, 13), (9, 40), (24, 8), (33, 16), (37, 53), (130, 250))
+CONTENTS = ("noise", "saturated", "flat", "ramp")
+QUALITIES = (1, 24, 25, 50, 75, 95, 100)
+SUBSAMPLINGS = (0, 2)
+
+
+def content(kind, H, W, seed=0):
+    """One u8 [H, W, 3] test image: uniform noise, 0 / 255 saturated noise, one flat colour, or a smooth ramp +- 6 noise."""
+    rng = np.random.default_rng([seed, H, W, len(kind)])
+    if kind == "noise":
+        return rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
+    if kind == "saturated":
+        return (rng.integers(0, 2, (H, W, 3)) * 255).astype(np.uint8)
+    if kind == "flat":
+        return np.full((H, W, 3), (200, 30, 90), np.uint8)
+    yy, xx = np.mgrid[0:H, 0:W]
+    ramp = np.stack([yy * 2 + xx, xx * 3 + yy // 2, 255 - yy - xx], -1) % 256
+    if kind == "ramp":
+        return np.clip(ramp + rng.integers(-6, 7, (H, W, 3)), 0, 255).astype(np.uint8)
+    raise ValueError(kind)
+
+
+def pillow_file(a, quality, sub, dpi=None):
+    import io
+    from PIL import Image
+    buf = io.BytesIO()
+    Image.fromarray(a).save(buf, format="jpeg", quality=quality, subsampling=sub, **({} if dpi is None else {"dpi": dpi}))
+    return buf.getvalue()
+
+
+def matrix():
+    """(H, W, kind, quality, subsampling) of every case.  The ramp cases at low quality already hold zero runs of 62."""
+    return [(H, W, kind, q, s) for (H, W) in GEOMETRIES for kind in CONTENTS for q in QUALITIES for s in SUBSAMPLINGS]
