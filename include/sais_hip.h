@@ -500,9 +500,9 @@ void sais_preprocess_plan_destroy(SaisPreprocessPlan* plan);
 #define SAIS_JPEG_E_CODE 1           /* invalid Huffman code, or a coefficient size beyond 8-bit baseline   */
 #define SAIS_JPEG_E_RUN 2            /* AC run past k = 63                                                  */
 #define SAIS_JPEG_E_MARKER 4         /* RST out of sequence, unexpected marker, or no marker ends the scan  */
-#define SAIS_JPEG_E_SHORT 8          /* entropy data ends before the last MCU of a restart interval         */
+#define SAIS_JPEG_E_SHORT 8          /* entropy data ends before the last MCU of a restart interval, or none */
 #define SAIS_JPEG_E_SYNC 16          /* speculative Huffman decode did not synchronise within the pass bound */
-#define SAIS_JPEG_E_RANGE 32         /* a dequantised coefficient outside int16 (not encoder output)         */
+#define SAIS_JPEG_E_RANGE 32         /* a dequantised coefficient or IDCT value out of range (no encoder's)   */
 typedef struct SaisJpegHuff {        /* one DHT table in decode form                                         */
     uint16_t lookup[512];            /* next 9 bits -> (code length << 8) | symbol; 0 = a code longer than 9 */
     int32_t maxcode[18];             /* largest code of length l (l = 1..16), -1 if none                     */

@@ -132,14 +132,14 @@ DEVINL bool is_rst(unsigned c) { return c >= 0xD0 && c <= 0xD7; }
 __global__ __launch_bounds__(NT) void jpeg_destuff(SaisJpegBatch b, const unsigned char* data, const SaisJpegHeader* hd,
                                                    WsPtrs w, int* status) {
     const int img = blockIdx.x, t = threadIdx.x;
-    __shared__ int s_end, s_bad, s_k[NT], s_r[NT], s_ktot, s_rtot;
+    __shared__ int s_end, s_bad, s_empty, s_k[NT], s_r[NT], s_ktot, s_rtot;
     if (status[img]) return;                                   // uniform across the workgroup
     const ImgRec r = w.rec[img];
     const unsigned char* d = data + hd[img].scan_offset;
     const long long L = hd[img].scan_bytes;
     const long long chunk = (L + NT - 1) / NT;
     const long long a = t * chunk, e = a + chunk < L ? a + chunk : L;
-    if (t == 0) { s_end = (int)L; s_bad = 0; }
+    if (t == 0) { s_end = (int)L; s_bad = 0; s_empty = 0; }
     __syncthreads();
     for (long long i = a; i < e; ++i) {                        // first marker that is not RSTn ends the scan
         if (d[i] == 0xFF) {
@@ -205,9 +205,14 @@ __global__ __launch_bounds__(NT) void jpeg_destuff(SaisJpegBatch b, const unsign
         int o = (k0 + 2 * s * SUB_BYTES + SUB_BYTES - 1) / SUB_BYTES * SUB_BYTES;
         sego[s] = o;
         sege[s] = o + (k1 - k0);
+        if (k1 == k0) s_empty = 1;                             // no subsequence would own the interval: nobody would miss its MCUs
     }
     __threadfence_block();
     __syncthreads();
+    if (s_empty) {
+        if (t == 0) atomicOr(&status[img], SAIS_JPEG_E_SHORT);
+        return;
+    }
     unsigned char* out = w.ds + r.ds_off;
     {
         int k = s_k[t], s = s_r[t];
@@ -542,6 +547,8 @@ __global__ __launch_bounds__(NT) void jpeg_idct(const SaisJpegHeader* hd, WsPtrs
     int big = 0;
     for (int i = 0; i < 64; ++i) big |= d[i] > 32767 || d[i] < -32768;
     if (big) { atomicOr(&status[img], SAIS_JPEG_E_RANGE); return; }
+    // The same holds past the 16-bit workspace of the SIMD column pass and past the range-limit table (row-pass output outside
+    // [-512, 511]), where jidctint.c wraps (`& RANGE_MASK`) and the SIMD IDCT saturates
     int ws[64];
     for (int col = 0; col < 8; ++col) {
         int o[8];
@@ -550,18 +557,20 @@ __global__ __launch_bounds__(NT) void jpeg_idct(const SaisJpegHeader* hd, WsPtrs
         } else {
             idct8<11>(d[col], d[8 + col], d[16 + col], d[24 + col], d[32 + col], d[40 + col], d[48 + col], d[56 + col], o);
         }
-        for (int i = 0; i < 8; ++i) ws[8 * i + col] = o[i];
+        for (int i = 0; i < 8; ++i) { ws[8 * i + col] = o[i]; big |= o[i] > 32767 || o[i] < -32768; }
     }
     unsigned char* dst = plane + (long long)(by * 8) * stride + bx * 8;
     for (int row = 0; row < 8; ++row) {
         const int* p = ws + 8 * row;
         int o[8];
         idct8<18>(p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], o);
+        for (int i = 0; i < 8; ++i) big |= o[i] > 511 || o[i] < -512;
         u32x2 pk;
         pk[0] = range_limit(o[0]) | range_limit(o[1]) << 8 | range_limit(o[2]) << 16 | range_limit(o[3]) << 24;
         pk[1] = range_limit(o[4]) | range_limit(o[5]) << 8 | range_limit(o[6]) << 16 | range_limit(o[7]) << 24;
         *(u32x2*)(dst + (long long)row * stride) = pk;
     }
+    if (big) atomicOr(&status[img], SAIS_JPEG_E_RANGE);
 }
 
 // ---------------------------------------------------------------- fancy upsampling + ycc_rgb_convert

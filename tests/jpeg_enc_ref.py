@@ -120,6 +120,25 @@ def scan_blocks(rgb, quality, sub):
     return coef, comp, dummy, edge
 
 
+def pack_bits(bits, lens):
+    """Codes (value int64 [n], bit count <= 32 [n]) in stream order -> (u8 bytes before stuffing, 1-bits padded at the end)."""
+    bits, lens = np.asarray(bits, np.int64), np.asarray(lens, np.int64)
+    table = (bits[:, None] >> np.arange(31, -1, -1)[None, :]) & 1
+    keep = np.arange(32)[None, :] >= (32 - lens)[:, None]
+    stream = table[keep].astype(np.uint8)                            # MSB-first bit string
+    pad = (-len(stream)) % 8
+    stream = np.concatenate([stream, np.ones(pad, np.uint8)])
+    return np.packbits(stream), pad
+
+
+def stuff(raw):
+    """u8 bytes -> (the bytes with 0x00 after every 0xFF, the 0xFF mask)."""
+    ff = raw == 0xFF
+    out = np.zeros(len(raw) + int(ff.sum()), np.uint8)
+    out[np.arange(len(raw)) + np.cumsum(ff) - ff] = raw
+    return out, ff
+
+
 def encode_scan(rgb, quality=75, sub=2):
     """u8 [H, W, 3] -> (bytes of the scan + EOI, statistics)."""
     coef, comp, dummy, edge = scan_blocks(np.asarray(rgb), quality, sub)
@@ -175,17 +194,8 @@ def encode_scan(rgb, quality=75, sub=2):
     lens.append(acl[tsel[eob], 0])
     keys, bits, lens = np.concatenate(keys), np.concatenate(bits), np.concatenate(lens)
     order = np.argsort(keys, kind="stable")
-    bits, lens = bits[order], lens[order]
-    # MSB-first bit string
-    table = (bits[:, None] >> np.arange(31, -1, -1)[None, :]) & 1
-    keep = np.arange(32)[None, :] >= (32 - lens)[:, None]
-    stream = table[keep].astype(np.uint8)
-    pad = (-len(stream)) % 8
-    stream = np.concatenate([stream, np.ones(pad, np.uint8)])
-    raw = np.packbits(stream)
-    ff = raw == 0xFF
-    out = np.zeros(len(raw) + int(ff.sum()), np.uint8)
-    out[np.arange(len(raw)) + np.concatenate([[0], np.cumsum(ff)[:-1]])] = raw
+    raw, pad = pack_bits(bits[order], lens[order])
+    out, ff = stuff(raw)
     stats = {
         "zrl": int(nzrl.sum()), "longest_run": int(run.max()) if len(run) else 0, "stuffed": int(ff.sum()),
         "dc_cat": int(size_of(diff).max()), "ac_cat": int(n.max()) if len(n) else 0,
