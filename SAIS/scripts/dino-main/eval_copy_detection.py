@@ -24,7 +24,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", ".."))
-from sais_amd import retrieval  # noqa: E402
+from sais_amd import imgfolder, retrieval  # noqa: E402
 from sais_amd.model_io import bool_flag, load_dino_backbone  # noqa: E402
 
 
@@ -53,7 +53,27 @@ def get_args_parser():
     return parser
 
 
+def get_cli_parser():
+    """The command line: the reference's flags (get_args_parser) + switches of this implementation only."""
+    parser = argparse.ArgumentParser('Copy detection on Copydays', parents=[get_args_parser()],
+                                     conflict_handler='resolve')          # -h comes with the parent
+    parser.add_argument('--gpu_loader', default=False, type=bool_flag,
+                        help="""Decode and transform the images on the GPU (sais_amd/imgfolder.py): the workers only read the
+        files.  The batches are bit-identical to the Pillow loader's.""")
+    return parser
+
+
+_gpu_loader = {}                                                   # device -> the GpuImageLoader of --gpu_loader (its buffers are reused)
+
+
 def extract(image_list, model, args, dev):
+    if getattr(args, "gpu_loader", False):
+        if dev not in _gpu_loader:
+            _gpu_loader[dev] = imgfolder.GpuImageLoader(dev)
+        loader = imgfolder.GpuBatches(torch.utils.data.DataLoader(
+            imgfolder.RawImgList(image_list), batch_size=args.batch_size_per_gpu, num_workers=args.num_workers, drop_last=False,
+            shuffle=False, collate_fn=imgfolder.collate_raw), lambda items: _gpu_loader[dev].square(items, args.imsize))
+        return retrieval.extract_features(retrieval.descriptor_features(model), loader, dev)
     ds = retrieval.ImgListDataset(image_list, args.imsize)
     loader = torch.utils.data.DataLoader(ds, batch_size=args.batch_size_per_gpu, num_workers=args.num_workers, drop_last=False,
                                          shuffle=False)
@@ -61,7 +81,7 @@ def extract(image_list, model, args, dev):
 
 
 def main(argv=None):
-    args = get_args_parser().parse_args(argv)
+    args = get_cli_parser().parse_args(argv)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         sys.exit("eval_copy_detection.py runs as one process on one GPU: multi-rank feature extraction is not implemented "
                  "(start it without a distributed launcher)")

@@ -20,7 +20,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", ".."))
-from sais_amd import knn  # noqa: E402
+from sais_amd import imgfolder, knn  # noqa: E402
 from sais_amd.model_io import bool_flag, load_dino_backbone  # noqa: E402
 
 
@@ -47,6 +47,16 @@ def get_args_parser():
     return parser
 
 
+def get_cli_parser():
+    """The command line: the reference's flags (get_args_parser) + switches of this implementation only."""
+    parser = argparse.ArgumentParser('Evaluation with weighted k-NN on ImageNet', parents=[get_args_parser()],
+                                     conflict_handler='resolve')          # -h comes with the parent
+    parser.add_argument('--gpu_loader', default=False, type=bool_flag,
+                        help="""Decode and transform the images on the GPU (sais_amd/imgfolder.py): the workers only read the
+        files.  The batches are bit-identical to the Pillow loader's.""")
+    return parser
+
+
 def build_model(args, dev):
     print(f"Model {args.arch} {args.patch_size}x{args.patch_size} built.")
     return load_dino_backbone(args, dev)
@@ -54,7 +64,14 @@ def build_model(args, dev):
 
 def extract_feature_pipeline(args, dev):
     loaders = []
+    gpu_loader = imgfolder.GpuImageLoader(dev) if getattr(args, "gpu_loader", False) else None
     for part in ("train", "val"):
+        if gpu_loader is not None:
+            ds = imgfolder.RawEvalFolder(os.path.join(args.data_path, part))
+            loaders.append(imgfolder.GpuBatches(torch.utils.data.DataLoader(
+                ds, batch_size=args.batch_size_per_gpu, num_workers=args.num_workers, drop_last=False, shuffle=False,
+                collate_fn=imgfolder.collate_raw), gpu_loader.eval))
+            continue
         ds = knn.EvalImageFolder(os.path.join(args.data_path, part))
         loaders.append(torch.utils.data.DataLoader(ds, batch_size=args.batch_size_per_gpu, num_workers=args.num_workers,
                                                    pin_memory=True, drop_last=False, shuffle=False))
@@ -78,7 +95,7 @@ def extract_feature_pipeline(args, dev):
 
 
 def main(argv=None):
-    args = get_args_parser().parse_args(argv)
+    args = get_cli_parser().parse_args(argv)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         sys.exit("eval_knn.py runs as one process on one GPU: multi-rank feature extraction is not implemented "
                  "(start it without a distributed launcher)")

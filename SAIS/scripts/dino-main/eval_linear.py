@@ -30,7 +30,7 @@ from pathlib import Path
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", ".."))
-from sais_amd import linear  # noqa: E402
+from sais_amd import imgfolder, linear  # noqa: E402
 from sais_amd.model_io import bool_flag, load_dino_backbone  # noqa: E402
 
 
@@ -62,10 +62,13 @@ def get_args_parser():
     # not in the reference
     parser.add_argument('--linear_weights', default='', type=str, help="With --evaluate: the classifier checkpoint to read.")
     parser.add_argument('--seed', default=0, type=int, help="Seed of the train transform's draws and of the heads' init.")
+    parser.add_argument('--gpu_loader', default=False, type=bool_flag,
+                        help="""Decode and transform the images on the GPU (sais_amd/imgfolder.py): the workers only read the
+        files.  The batches are bit-identical to the Pillow loader's.""")
     return parser
 
 
-EXTRA_FLAGS = ("linear_weights", "seed")
+EXTRA_FLAGS = ("linear_weights", "seed", "gpu_loader")
 
 
 def build_model(args, dev):
@@ -168,9 +171,16 @@ def eval_linear(args):
     lrs = [v * args.batch_size_per_gpu / 256. for v in base]                       # linear scaling rule, world size 1
     probe = linear.LinearProbe(embed_dim, args.num_labels, lrs, args.epochs, momentum=0.9, device=dev, seed=args.seed)
 
-    dataset_val = linear.LabelledEvalFolder(os.path.join(args.data_path, "val"))
-    val_loader = torch.utils.data.DataLoader(dataset_val, batch_size=args.batch_size_per_gpu, num_workers=args.num_workers,
-                                             pin_memory=True)
+    gpu_loader = imgfolder.GpuImageLoader(dev) if args.gpu_loader else None
+    if gpu_loader is not None:
+        dataset_val = imgfolder.RawLabelledEvalFolder(os.path.join(args.data_path, "val"))
+        val_loader = imgfolder.GpuBatches(torch.utils.data.DataLoader(
+            dataset_val, batch_size=args.batch_size_per_gpu, num_workers=args.num_workers, collate_fn=imgfolder.collate_raw),
+            gpu_loader.eval)
+    else:
+        dataset_val = linear.LabelledEvalFolder(os.path.join(args.data_path, "val"))
+        val_loader = torch.utils.data.DataLoader(dataset_val, batch_size=args.batch_size_per_gpu, num_workers=args.num_workers,
+                                                 pin_memory=True)
     if args.evaluate:
         for i, p in enumerate(files):
             ckpt = torch.load(p, map_location="cpu", weights_only=False)
@@ -180,10 +190,17 @@ def eval_linear(args):
             print(f"Accuracy of the network on the {len(dataset_val)} test images{tag}: {s['acc1']:.1f}%")
         return
 
-    dataset_train = linear.TrainImageFolder(os.path.join(args.data_path, "train"), seed=args.seed)
-    sampler = linear.EpochSampler(len(dataset_train))
-    train_loader = torch.utils.data.DataLoader(dataset_train, sampler=sampler, batch_size=args.batch_size_per_gpu,
-                                               num_workers=args.num_workers, pin_memory=True)
+    if gpu_loader is not None:
+        dataset_train = imgfolder.RawTrainFolder(os.path.join(args.data_path, "train"), seed=args.seed)
+        sampler = linear.EpochSampler(len(dataset_train))
+        train_loader = imgfolder.GpuBatches(torch.utils.data.DataLoader(
+            dataset_train, sampler=sampler, batch_size=args.batch_size_per_gpu, num_workers=args.num_workers,
+            collate_fn=imgfolder.collate_raw), gpu_loader.train)
+    else:
+        dataset_train = linear.TrainImageFolder(os.path.join(args.data_path, "train"), seed=args.seed)
+        sampler = linear.EpochSampler(len(dataset_train))
+        train_loader = torch.utils.data.DataLoader(dataset_train, sampler=sampler, batch_size=args.batch_size_per_gpu,
+                                                   num_workers=args.num_workers, pin_memory=True)
     print(f"Data loaded with {len(dataset_train)} train and {len(dataset_val)} val imgs.")
 
     # Optionally resume from a checkpoint (every head of the run, or none)

@@ -531,6 +531,19 @@ size_t sais_jpeg_workspace_bytes(int n, int height, int width, int64_t total_sca
 int    sais_jpeg_decode(const SaisJpegBatch* batch, const unsigned char* data, const SaisJpegHeader* headers,
                         void* workspace, size_t workspace_bytes, unsigned char* out /* [n,H,W,3] */, int* status,
                         void* stream);
+/* The same decode for a batch of mixed sizes: the same files, arithmetic and status bits, every image with the height and
+ * width of its own header.  Image i is a contiguous uint8 [h_i, w_i, 3] at out + out_offset[i] (bytes; the layout is the
+ * caller's, e.g. the running sum of h * w * 3).  Headers and offsets are passed twice, as the augment entries take their
+ * table: the host copies size the workspace and the launch grids and are checked by the entry (SAIS_ERR_ARG and no launch
+ * for an offset outside `out`, a workspace below sais_jpeg_mixed_workspace_bytes, scan bytes beyond data_bytes, n outside
+ * 1..65535), the device copies are what the kernels read.  An image whose device header does not fit the regions and grids
+ * the host copy sized, or whose device offset leaves `out`, gets SAIS_JPEG_E_MARKER and writes nothing.  The workspace grows
+ * with the sum of the images' own sizes (coefficients and planes are laid out by prefix sums), not with n x the largest.   */
+size_t sais_jpeg_mixed_workspace_bytes(const SaisJpegHeader* headers_host, int n);
+int    sais_jpeg_decode_mixed(int n, const unsigned char* data, int64_t data_bytes, const SaisJpegHeader* headers_host,
+                              const SaisJpegHeader* headers_dev, const int64_t* out_offset_host, const int64_t* out_offset_dev,
+                              void* workspace, size_t workspace_bytes, unsigned char* out, size_t out_bytes, int* status,
+                              void* stream);
 
 /* ---------------------------------------------------------------- JPEG encode (uint8 RGB on the device -> scan bytes)
  * The counterpart of the decoder for images made on the device (attention heat maps, colour-coded flow): baseline sequential,
@@ -588,6 +601,35 @@ int    sais_augment_crop_resize(const unsigned char* frames, int nframes, int he
 int    sais_augment_color(const unsigned char* views_u8, size_t views_u8_bytes, const SaisAugView* views_host,
                           const SaisAugView* views_dev, int nviews, const float* lut, float* out, size_t out_elems,
                           void* stream);
+
+/* ---------------------------------------------------------------- image-folder transforms (uint8 images -> float32 batches)
+ * The Pillow transforms of the evaluation tools' datasets (knn.EvalImageFolder: Resize(256, bicubic) + CenterCrop(224);
+ * linear.TrainImageFolder: crop box, bilinear to 224 x 224, flip; retrieval.ImgListDataset: bicubic to imsize x imsize), each
+ * followed by ToTensor + Normalize, on decoded images of any size packed in one uint8 buffer.  Image i -> float32
+ * [3,out_h,out_w] at out + out_offset (elements), bit-identical to
+ *   img.crop(box).resize((rw, rh), filter).crop((win_left, win_top, win_left + out_w, win_top + out_h)) [.transpose(FLIP_LEFT_RIGHT)]
+ * through `lut` (device float [3][256], the normalised value of every byte per channel).  Only the window is evaluated.
+ * The table is passed twice, as the augment entries take theirs: SAIS_ERR_ARG and nothing launched for out_h / out_w outside
+ * 1..SAIS_IMG_MAX_OUT, an empty box or one outside the image, a window that leaves the resampled image, a filter that is
+ * neither, an offset outside the buffers, or a descriptor whose one-row band does not fit in LDS (a downscale of several
+ * hundred to one: sais_image_transform_fits, a host function, answers 0 for it, so a caller can route it elsewhere first). */
+#define SAIS_IMG_MAX_OUT 512
+#define SAIS_IMG_BILINEAR 0
+#define SAIS_IMG_BICUBIC 1
+typedef struct SaisImgXform {
+    int64_t src_offset;              /* bytes, into src: the image is uint8 [src_h, src_w, 3]                  */
+    int src_h, src_w;
+    int box[4];                      /* left, top, right, bottom: cropped first                               */
+    int rw, rh;                      /* the box is resampled to rw x rh                                        */
+    int win_left, win_top;           /* origin of the out_w x out_h window inside the resampled image         */
+    int filter;                      /* SAIS_IMG_BILINEAR (support 1) or SAIS_IMG_BICUBIC (support 2, a = -0.5) */
+    int flip;
+    int64_t out_offset;              /* float elements, into out                                              */
+} SaisImgXform;
+int    sais_image_transform_fits(const SaisImgXform* d, int out_h, int out_w);
+int    sais_image_transform(const unsigned char* src, size_t src_bytes, const SaisImgXform* table_host,
+                            const SaisImgXform* table_dev, int n, int out_h, int out_w, const float* lut, float* out,
+                            size_t out_elems, void* stream);
 
 /* ---------------------------------------------------------------- temporal encoder glue (dim 384, 4 heads x 96)
  * prepareInputForTransformer, prepare_model.py:179-195: z[b,0] = frame_cls, z[b,1+t] = x[b,t] + pos[t]

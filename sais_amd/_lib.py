@@ -101,6 +101,12 @@ class SaisAugView(ctypes.Structure):
                 ("reserved", c_int), ("u8_offset", ctypes.c_int64), ("out_offset", ctypes.c_int64)]
 
 
+class SaisImgXform(ctypes.Structure):
+    _fields_ = [("src_offset", ctypes.c_int64), ("src_h", c_int), ("src_w", c_int), ("box", c_int * 4), ("rw", c_int),
+                ("rh", c_int), ("win_left", c_int), ("win_top", c_int), ("filter", c_int), ("flip", c_int),
+                ("out_offset", ctypes.c_int64)]
+
+
 OP_VIT_BLOCK_FWD, OP_VIT_BLOCK_BWD, OP_TEMPORAL_LAYER_FWD, OP_TEMPORAL_LAYER_BWD = 0, 1, 2, 3
 
 
@@ -190,6 +196,9 @@ SIGNATURES = {
     "sais_jpeg_parse": [c_void_p, ctypes.c_size_t, c_void_p],
     "sais_jpeg_workspace_bytes": [c_int, c_int, c_int, ctypes.c_int64, c_int],
     "sais_jpeg_decode": [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p],
+    "sais_jpeg_mixed_workspace_bytes": [c_void_p, c_int],
+    "sais_jpeg_decode_mixed": [c_int, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_size_t,
+                               c_void_p, ctypes.c_size_t, c_void_p, c_void_p],
     "sais_jpeg_encode_bound": [c_int, c_int, c_int],
     "sais_jpeg_encode_workspace_bytes": [c_int, c_int, c_int, c_int],
     "sais_jpeg_encode": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t, c_void_p,
@@ -199,6 +208,10 @@ SIGNATURES = {
                                  ctypes.c_size_t, c_void_p],
     "sais_augment_color": [c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_int, c_void_p, c_void_p, ctypes.c_size_t,
                            c_void_p],
+    # image-folder transforms (csrc/imgfolder.hip)
+    "sais_image_transform_fits": [c_void_p, c_int, c_int],
+    "sais_image_transform": [c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                             ctypes.c_size_t, c_void_p],
     "sais_scale_f32": [c_void_p, c_long, c_float, c_void_p],
     "sais_touch": [c_void_p, c_long, c_void_p],
     "sais_temporal_prepare_fwd": [c_void_p, c_long, c_long, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
@@ -308,6 +321,7 @@ def load():
     lib.sais_preprocess_plan_destroy.restype = None
     lib.sais_workspace_bytes.restype = ctypes.c_size_t
     lib.sais_jpeg_workspace_bytes.restype = ctypes.c_size_t
+    lib.sais_jpeg_mixed_workspace_bytes.restype = ctypes.c_size_t
     lib.sais_jpeg_encode_bound.restype = ctypes.c_size_t
     lib.sais_jpeg_encode_workspace_bytes.restype = ctypes.c_size_t
     lib.sais_augment_workspace_bytes.restype = ctypes.c_size_t

@@ -17,10 +17,11 @@
 #include <cstring>
 
 #include "common.hpp"
+#include "resample.hpp"
 #include "../../include/sais_hip.h"
 
 namespace {
-constexpr int PRECISION_BITS = 32 - 8 - 2;
+using namespace resample;
 constexpr int MAX_SIZE = SAIS_AUG_MAX_SIZE;
 constexpr int RESIZE_THREADS = 256;
 constexpr int COLOR_THREADS = 1024;
@@ -31,56 +32,7 @@ enum { OP_BRIGHTNESS = 0, OP_CONTRAST = 1, OP_SATURATION = 2, OP_HUE = 3, OP_GRA
 struct Border { int left, top, width, height; };
 
 // ---------------------------------------------------------------------------------------------- resampling geometry
-struct Axis {
-    double scale, support, ss;
-    int in, ksize;
-};
-
-__host__ __device__ inline Axis make_axis(int in, int out) {       // Resample.c precompute_coeffs, box = whole axis
-    Axis a;
-    a.in = in;
-    a.scale = (double)in / out;
-    const double filterscale = a.scale < 1.0 ? 1.0 : a.scale;
-    a.support = 2.0 * filterscale;                                    // bicubic: support 2
-    a.ksize = (int)ceil(a.support) * 2 + 1;
-    a.ss = 1.0 / filterscale;
-    return a;
-}
-
-__host__ __device__ inline void axis_bounds(const Axis& a, int xx, int& xmin, int& cnt, double& center) {
-    center = (xx + 0.5) * a.scale;
-    xmin = (int)(center - a.support + 0.5);
-    if (xmin < 0) xmin = 0;
-    int xmax = (int)(center + a.support + 0.5);
-    if (xmax > a.in) xmax = a.in;
-    cnt = xmax - xmin;
-}
-
-__host__ __device__ inline double bicubic(double x) {
-    const double a = -0.5;
-    if (x < 0.0) x = -x;
-    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
-    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
-    return 0.0;
-}
-
-// coefficient row of output index xx: normalised in double, then normalize_coeffs_8bpc
-__device__ inline void axis_coefs(const Axis& a, int xx, int* k, int& xmin, int& cnt) {
-    double center;
-    axis_bounds(a, xx, xmin, cnt, center);
-    double ww = 0.0;
-    for (int x = 0; x < cnt; ++x) ww += bicubic((x + xmin - center + 0.5) * a.ss);
-    for (int x = 0; x < cnt; ++x) {
-        double w = bicubic((x + xmin - center + 0.5) * a.ss);
-        if (ww != 0.0) w /= ww;
-        k[x] = w < 0 ? (int)(-0.5 + w * (1 << PRECISION_BITS)) : (int)(0.5 + w * (1 << PRECISION_BITS));
-    }
-}
-
-// input rows a band of `band` output rows can touch: first rows of its first and last output row are at most
-// (band - 1) * scale + 1 apart, and no row has more than ksize taps
-__host__ __device__ inline int band_rows_bound(const Axis& ay, int band) { return (int)((band - 1) * ay.scale) + 2 + ay.ksize; }
-
+// (resample.hpp: Axis, make_axis, axis_coefs, band_rows_bound, clip8; every view here is bicubic)
 __host__ __device__ inline int resize_lds_bytes(int S, const Axis& ax, const Axis& ay, int band) {
     const int ints = S * ax.ksize + 2 * S + band * ay.ksize + 2 * band;
     return ints * 4 + ((band_rows_bound(ay, band) * S * 3 + 15) & ~15);
@@ -98,11 +50,6 @@ __host__ __device__ inline bool view_geometry_ok(const SaisAugView& v, int nfram
     if (v.frame < 0 || v.frame >= nframes) return false;
     return v.box[0] >= 0 && v.box[1] >= 0 && v.box[2] > v.box[0] && v.box[3] > v.box[1] && v.box[2] <= b.width &&
            v.box[3] <= b.height;
-}
-
-__device__ inline int clip8(int acc) {
-    const int v = acc >> PRECISION_BITS;
-    return v < 0 ? 0 : (v > 255 ? 255 : v);
 }
 
 __global__ __launch_bounds__(RESIZE_THREADS) void crop_resize_kernel(const unsigned char* __restrict__ frames, int nframes,

@@ -3,7 +3,7 @@
 // defaults.  tests/jpeg_ref.py restates every rule in numpy.
 //
 // Phases (one stable kernel name each):
-//   jpeg_layout      per-image regions of the workspace, header checks
+//   jpeg_layout      per-image regions of the workspace (prefix sums of the images' own sizes), header checks
 //   jpeg_destuff     one workgroup per image: drop stuffed 0x00 / fill 0xFF, cut at RSTn, stop at any other marker.
 //                    Restart segment s is written at a SUB_BYTES-aligned offset, so a segment start is always the
 //                    start of a subsequence (a hard sync point) and every segment is followed by >= SUB_BYTES zeros.
@@ -16,6 +16,10 @@
 //   jpeg_idct        jidctint.c jpeg_idct_islow, one thread per block, into padded uint8 planes
 //   jpeg_color       fancy upsampling (jdsample.c) + ycc_rgb_convert (jdcolor.c) -> interleaved RGB
 // Decoder state at a codeword start: (bit position, block slot within the MCU, zig-zag index k).
+//
+// Every image carries its own geometry in its ImgRec.  sais_jpeg_decode (one geometry per batch, output [n,H,W,3]) and
+// sais_jpeg_decode_mixed (any geometry per image, output at the caller's offsets) run the same kernels; launch grids are
+// sized by the largest image and threads past an image's own count return.
 #include "common.hpp"
 #include "../../include/sais_hip.h"
 #include <string.h>
@@ -29,7 +33,12 @@ constexpr int NT = 256;
 
 struct ImgRec {
     long long ds_off;                     // destuffed region of the image (bytes, SUB_BYTES-aligned)
+    long long coef_off;                   // first block of the image in the coefficient region
+    long long plane_off;                  // its planes (bytes): Y first, then Cb, Cr of cplane bytes each
+    long long yplane, cplane;
+    long long out_off;                    // its uint8 [H,W,3] output (bytes into out)
     int ds_cap, sub_base, nsub, seg_base, nseg;
+    int H, W;
     int mcux, mcuy, bpm, ny, hs, vs, ri, blocks;
     int ystride, cstride;                 // padded plane widths
 };
@@ -37,23 +46,41 @@ struct ImgRec {
 struct Layout {
     size_t rec, segk, sego, sege, ds, en, ex, base, flags, coef, planes, total;
     long long ds_cap, nsub;
-    long long coef_blocks;                // per image
-    long long plane_bytes, yplane;        // per image; Y plane first, then Cb, Cr of cplane bytes each
-    long long cplane;
+    long long coef_cap;                   // blocks of the whole batch
+    long long plane_cap;                  // plane bytes of the whole batch
 };
 
 static inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
-static Layout layout_of(int n, int H, int W, long long scan_bytes, int segments) {
+// What a header says about its image: sampling, MCU grid, blocks, plane sizes.  False for a header no kernel may follow.
+__host__ __device__ inline bool image_geometry(const SaisJpegHeader& h, ImgRec& r) {
+    const int hs = h.hsamp, vs = h.vsamp;
+    if (!((hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2))) return false;
+    if (h.height < 1 || h.height > 65535 || h.width < 1 || h.width > 65535 || h.restart_interval < 0) return false;
+    r.hs = hs; r.vs = vs; r.H = h.height; r.W = h.width;
+    r.mcux = (h.width + 8 * hs - 1) / (8 * hs);
+    r.mcuy = (h.height + 8 * vs - 1) / (8 * vs);
+    r.ny = hs * vs;
+    r.bpm = r.ny + 2;
+    r.ri = h.restart_interval;
+    r.blocks = r.mcux * r.mcuy * r.bpm;
+    r.ystride = r.mcux * hs * 8;
+    r.cstride = r.mcux * 8;
+    r.yplane = (long long)r.ystride * r.mcuy * vs * 8;
+    r.cplane = (long long)r.cstride * r.mcuy * 8;
+    const int mcus = r.mcux * r.mcuy;
+    r.nseg = r.ri ? (mcus + r.ri - 1) / r.ri : 1;
+    return true;
+}
+
+__host__ __device__ inline long long plane_bytes_of(const ImgRec& r) { return (r.yplane + 2 * r.cplane + 255) & ~255LL; }
+__host__ __device__ inline long long quads_of(const ImgRec& r) { return (long long)r.H * ((r.W + 3) / 4); }
+
+// regions for `coef_cap` blocks and `plane_cap` plane bytes in all
+static Layout layout_sums(int n, long long scan_bytes, int segments, long long coef_cap, long long plane_cap) {
     Layout L{};
-    long long bx8 = (W + 7) / 8, by8 = (H + 7) / 8, bx16 = (W + 15) / 16, by16 = (H + 15) / 16;
-    long long cb = 3 * bx8 * by8;
-    if (4 * bx16 * by8 > cb) cb = 4 * bx16 * by8;
-    if (6 * bx16 * by16 > cb) cb = 6 * bx16 * by16;
-    L.coef_blocks = cb;
-    L.yplane = bx16 * 16 * by16 * 16;
-    L.cplane = bx8 * 8 * by8 * 8;
-    L.plane_bytes = (L.yplane + 2 * L.cplane + 255) & ~255LL;
+    L.coef_cap = coef_cap;
+    L.plane_cap = plane_cap;
     L.ds_cap = scan_bytes + 2LL * SUB_BYTES * segments + 3LL * SUB_BYTES * n;
     L.ds_cap = (L.ds_cap + SUB_BYTES - 1) / SUB_BYTES * SUB_BYTES;
     L.nsub = L.ds_cap / SUB_BYTES;
@@ -67,10 +94,42 @@ static Layout layout_of(int n, int H, int W, long long scan_bytes, int segments)
     L.ex = o;     o = al(o + 8 * (size_t)L.nsub);
     L.base = o;   o = al(o + 4 * (size_t)L.nsub);
     L.flags = o;  o = al(o + 4 * (size_t)MAX_PASSES * n);
-    L.coef = o;   o = al(o + 128 * (size_t)cb * n);
-    L.planes = o; o = al(o + (size_t)L.plane_bytes * n);
+    L.coef = o;   o = al(o + 128 * (size_t)coef_cap);
+    L.planes = o; o = al(o + (size_t)plane_cap);
     L.total = o;
     return L;
+}
+
+// one geometry per batch: n slots of the largest block count and plane size any sampling gives that geometry
+static Layout layout_of(int n, int H, int W, long long scan_bytes, int segments, int* max_blocks) {
+    long long bx8 = (W + 7) / 8, by8 = (H + 7) / 8, bx16 = (W + 15) / 16, by16 = (H + 15) / 16;
+    long long cb = 3 * bx8 * by8;
+    if (4 * bx16 * by8 > cb) cb = 4 * bx16 * by8;
+    if (6 * bx16 * by16 > cb) cb = 6 * bx16 * by16;
+    const long long yplane = bx16 * 16 * by16 * 16, cplane = bx8 * 8 * by8 * 8;
+    const long long plane_bytes = (yplane + 2 * cplane + 255) & ~255LL;
+    if (max_blocks) *max_blocks = (int)cb;
+    return layout_sums(n, scan_bytes, segments, cb * n, plane_bytes * n);
+}
+
+// any geometry per image: the sums of the images' own sizes.  A header image_geometry refuses adds nothing (jpeg_layout
+// flags it and gives it no region).
+struct MixedSums { long long scan, blocks, planes, max_quads, segments; int max_blocks; };
+constexpr long long MAX_SEGMENTS = 1LL << 30;   // of a batch: the segment tables are indexed by int
+
+static MixedSums mixed_sums(const SaisJpegHeader* hd, int n) {
+    MixedSums m{};
+    for (int i = 0; i < n; ++i) {
+        ImgRec r{};
+        if (!image_geometry(hd[i], r) || hd[i].scan_bytes <= 0 || hd[i].scan_bytes >= (1LL << 28)) continue;
+        m.scan += hd[i].scan_bytes;
+        m.segments += r.nseg;
+        m.blocks += r.blocks;
+        m.planes += plane_bytes_of(r);
+        if (r.blocks > m.max_blocks) m.max_blocks = r.blocks;
+        if (quads_of(r) > m.max_quads) m.max_quads = quads_of(r);
+    }
+    return m;
 }
 
 __constant__ unsigned char k_natural[64] = {
@@ -81,46 +140,49 @@ __constant__ unsigned char k_natural[64] = {
 struct WsPtrs {
     ImgRec* rec; int* segk; int* sego; int* sege; unsigned char* ds; unsigned long long* en; unsigned long long* ex;
     int* base; int* flags; short* coef; unsigned char* planes;
-    long long coef_blocks, plane_bytes, yplane, cplane, nsub;
+    long long coef_cap, plane_cap, nsub;
+};
+
+// What jpeg_layout holds every image against.  uniform: every header has the batch geometry and image i is slot i of
+// out [n,H,W,3]; otherwise out_off is the caller's table of byte offsets into out (out_bytes long).
+struct Geo {
+    int uniform, max_blocks;
+    long long max_quads, out_bytes;
+    const long long* out_off;
 };
 
 // ---------------------------------------------------------------- layout + header checks (one thread)
-__global__ void jpeg_layout(SaisJpegBatch b, const SaisJpegHeader* hd, WsPtrs w, long long ds_cap, int* status) {
+__global__ void jpeg_layout(SaisJpegBatch b, const SaisJpegHeader* hd, WsPtrs w, long long ds_cap, Geo g, int* status) {
     if (threadIdx.x != 0) return;
-    long long ds = 0, scan = 0;
+    long long ds = 0, scan = 0, coef = 0, planes = 0;
     int sub = 0, seg = 0;
     for (int i = 0; i < b.n; ++i) {
         const SaisJpegHeader& h = hd[i];
         ImgRec r{};
-        int hs = h.hsamp, vs = h.vsamp;
-        bool ok = h.height == b.height && h.width == b.width &&
-                  ((hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2)) && h.restart_interval >= 0 &&
-                  h.scan_offset >= 0 && h.scan_bytes > 0 && h.scan_bytes < (1LL << 28) &&
+        bool ok = image_geometry(h, r) && h.scan_offset >= 0 && h.scan_bytes > 0 && h.scan_bytes < (1LL << 28) &&
                   h.scan_offset + h.scan_bytes <= b.data_bytes;
+        if (g.uniform) ok = ok && h.height == b.height && h.width == b.width;
         for (int c = 0; c < 3; ++c)
             ok = ok && h.qsel[c] >= 0 && h.qsel[c] < 4 && h.dcsel[c] >= 0 && h.dcsel[c] < 2 && h.acsel[c] >= 0 &&
                  h.acsel[c] < 2;
-        r.hs = hs; r.vs = vs;
-        r.mcux = (b.width + 8 * hs - 1) / (8 * hs);
-        r.mcuy = (b.height + 8 * vs - 1) / (8 * vs);
-        r.ny = hs * vs;
-        r.bpm = r.ny + 2;
-        r.ri = h.restart_interval;
-        r.blocks = r.mcux * r.mcuy * r.bpm;
-        r.ystride = r.mcux * hs * 8;
-        r.cstride = r.mcux * 8;
-        int mcus = r.mcux * r.mcuy;
-        r.nseg = r.ri ? (mcus + r.ri - 1) / r.ri : 1;
-        long long cap = (h.scan_bytes + 2LL * SUB_BYTES * r.nseg + 2 * SUB_BYTES + SUB_BYTES - 1) / SUB_BYTES * SUB_BYTES;
-        ok = ok && scan + h.scan_bytes <= b.total_scan_bytes && seg + r.nseg <= b.total_segments &&
-             ds + cap <= ds_cap && cap < (1LL << 29) && (long long)r.blocks <= w.coef_blocks;
+        long long cap = 0, pb = 0;
+        if (ok) {
+            cap = (h.scan_bytes + 2LL * SUB_BYTES * r.nseg + 2 * SUB_BYTES + SUB_BYTES - 1) / SUB_BYTES * SUB_BYTES;
+            pb = plane_bytes_of(r);
+            r.out_off = g.uniform ? (long long)i * b.height * b.width * 3 : g.out_off[i];
+            // a header larger than the workspace or the launch grids allow, or an output outside `out`: flagged, nothing written
+            ok = scan + h.scan_bytes <= b.total_scan_bytes && seg + r.nseg <= b.total_segments && ds + cap <= ds_cap &&
+                 cap < (1LL << 29) && coef + r.blocks <= w.coef_cap && planes + pb <= w.plane_cap &&
+                 r.blocks <= g.max_blocks && quads_of(r) <= g.max_quads && r.out_off >= 0 &&
+                 r.out_off + (long long)r.H * r.W * 3 <= g.out_bytes;
+        }
+        r.ds_off = ds; r.sub_base = sub; r.seg_base = seg; r.coef_off = coef; r.plane_off = planes;
         if (!ok) {
             status[i] |= SAIS_JPEG_E_MARKER;
             r.nseg = 0; r.nsub = 0; r.blocks = 0;
-            r.ds_off = ds; r.sub_base = sub; r.seg_base = seg;
         } else {
-            r.ds_off = ds; r.ds_cap = (int)cap; r.sub_base = sub; r.nsub = (int)(cap / SUB_BYTES); r.seg_base = seg;
-            ds += cap; sub += r.nsub; seg += r.nseg; scan += h.scan_bytes;
+            r.ds_cap = (int)cap; r.nsub = (int)(cap / SUB_BYTES);
+            ds += cap; sub += r.nsub; seg += r.nseg; scan += h.scan_bytes; coef += r.blocks; planes += pb;
         }
         w.rec[i] = r;
     }
@@ -439,7 +501,7 @@ __global__ __launch_bounds__(NT) void jpeg_huff_write(int n, const SaisJpegHeade
     if (blk >= bhi) return;                                    // data after the interval's last MCU: ignored
     if (c >= r.bpm || k >= 64 || blk < blo || blk % r.bpm != c) { atomicOr(&status[si.img], SAIS_JPEG_E_SYNC); return; }
     Dec x = make_dec(w, hd[si.img], r);
-    short* coef = w.coef + (long long)si.img * w.coef_blocks * 64;
+    short* coef = w.coef + r.coef_off * 64;
     unsigned stop = si.last ? si.seg_end_bits + 8u * SUB_BYTES : si.sub_end_bits;
     int err = 0, count = 0;
     run<true>(x, pos, c, k, stop, si.seg_end_bits, blk, blo, bhi, coef, err, count);
@@ -455,7 +517,7 @@ __global__ __launch_bounds__(NT) void jpeg_dc_scan(WsPtrs w, const int* status) 
     const ImgRec r = w.rec[img];
     const int per = comp == 0 ? r.ny : 1, off = comp == 0 ? 0 : r.ny + comp - 1;
     const int mcus = r.mcux * r.mcuy, total = mcus * per;
-    short* coef = w.coef + (long long)img * w.coef_blocks * 64;
+    short* coef = w.coef + r.coef_off * 64;
     const int chunk = (total + NT - 1) / NT, a = t * chunk, e = a + chunk < total ? a + chunk : total;
     auto at = [&](int q) -> short* { return coef + ((long long)(q / per) * r.bpm + off + q % per) * 64; };
     auto starts = [&](int q) { return q % per == 0 && r.ri && (q / per) % r.ri == 0; };
@@ -529,11 +591,11 @@ __global__ __launch_bounds__(NT) void jpeg_idct(const SaisJpegHeader* hd, WsPtrs
     const int mcu = b / r.bpm, slot = b - mcu * r.bpm, mx = mcu % r.mcux, my = mcu / r.mcux;
     const int comp = slot < r.ny ? 0 : slot - r.ny + 1;
     int bx, by, stride;
-    unsigned char* plane = w.planes + (long long)img * w.plane_bytes;
+    unsigned char* plane = w.planes + r.plane_off;
     if (comp == 0) { bx = mx * r.hs + slot % r.hs; by = my * r.vs + slot / r.hs; stride = r.ystride; }
-    else { bx = mx; by = my; stride = r.cstride; plane += w.yplane + (comp - 1) * w.cplane; }
+    else { bx = mx; by = my; stride = r.cstride; plane += r.yplane + (comp - 1) * r.cplane; }
     const uint16_t* q = hd[img].quant[hd[img].qsel[comp]];
-    const short* cp = w.coef + ((long long)img * w.coef_blocks + b) * 64;
+    const short* cp = w.coef + (r.coef_off + b) * 64;
     int d[64];
     for (int i = 0; i < 8; ++i) {
         u32x4 v = *(const u32x4*)(cp + 8 * i);
@@ -595,17 +657,18 @@ DEVINL int chroma(const unsigned char* p, int stride, int dw, int dh, int hs, in
 
 DEVINL unsigned clamp255(int v) { return v < 0 ? 0u : v > 255 ? 255u : (unsigned)v; }
 
-__global__ __launch_bounds__(NT) void jpeg_color(int H, int W, WsPtrs w, const int* status, unsigned char* out) {
+__global__ __launch_bounds__(NT) void jpeg_color(WsPtrs w, const int* status, unsigned char* out) {
     const int img = blockIdx.y;
     if (status[img]) return;
+    const ImgRec& r = w.rec[img];
+    const int H = r.H, W = r.W;
     const int qw = (W + 3) / 4;
     const long long gid = (long long)blockIdx.x * NT + threadIdx.x;
     if (gid >= (long long)H * qw) return;
     const int y = (int)(gid / qw), x0 = (int)(gid % qw) * 4;
-    const ImgRec& r = w.rec[img];
-    const unsigned char* yp = w.planes + (long long)img * w.plane_bytes;
-    const unsigned char* cbp = yp + w.yplane;
-    const unsigned char* crp = cbp + w.cplane;
+    const unsigned char* yp = w.planes + r.plane_off;
+    const unsigned char* cbp = yp + r.yplane;
+    const unsigned char* crp = cbp + r.cplane;
     const int dw = (W + r.hs - 1) / r.hs, dh = (H + r.vs - 1) / r.vs;
     unsigned char px[12];
     const int np = W - x0 < 4 ? W - x0 : 4;
@@ -618,7 +681,7 @@ __global__ __launch_bounds__(NT) void jpeg_color(int H, int W, WsPtrs w, const i
         px[3 * e + 1] = (unsigned char)clamp255(Y + ((-22554 * cb + 32768 - 46802 * cr) >> 16));
         px[3 * e + 2] = (unsigned char)clamp255(Y + ((116130 * cb + 32768) >> 16));
     }
-    unsigned char* dst = out + (((long long)img * H + y) * W + x0) * 3;
+    unsigned char* dst = out + r.out_off + ((long long)y * W + x0) * 3;
     if (np == 4 && ((uintptr_t)dst & 3) == 0) {
         unsigned* d32 = (unsigned*)dst;
         for (int i = 0; i < 3; ++i)
@@ -766,9 +829,38 @@ extern "C" int sais_jpeg_parse(const unsigned char* data, size_t n, SaisJpegHead
     }
 }
 
+namespace {
+// every phase, for a batch whose regions `L` and limits `g` the entry has fixed
+int launch_decode(const SaisJpegBatch& b, const unsigned char* data, const SaisJpegHeader* headers, unsigned char* ws,
+                  const Layout& L, const Geo& g, unsigned char* out, int* status, hipStream_t st) {
+    WsPtrs w;
+    w.rec = (ImgRec*)(ws + L.rec); w.segk = (int*)(ws + L.segk); w.sego = (int*)(ws + L.sego);
+    w.sege = (int*)(ws + L.sege); w.ds = ws + L.ds; w.en = (unsigned long long*)(ws + L.en);
+    w.ex = (unsigned long long*)(ws + L.ex); w.base = (int*)(ws + L.base); w.flags = (int*)(ws + L.flags);
+    w.coef = (short*)(ws + L.coef); w.planes = ws + L.planes;
+    w.coef_cap = L.coef_cap; w.plane_cap = L.plane_cap; w.nsub = L.nsub;
+    hipError_t e = hipMemsetAsync(status, 0, sizeof(int) * b.n, st);
+    if (e == hipSuccess) e = hipMemsetAsync(ws + L.ds, 0, L.en - L.ds, st);              // zero gaps between segments
+    if (e == hipSuccess) e = hipMemsetAsync(ws + L.flags, 0, L.planes - L.flags, st);    // pass flags + coefficients
+    if (e != hipSuccess) { sais_set_last_error((int)e); return SAIS_ERR_LAUNCH; }
+    hipLaunchKernelGGL(jpeg_layout, dim3(1), dim3(64), 0, st, b, headers, w, L.ds_cap, g, status);
+    hipLaunchKernelGGL(jpeg_destuff, dim3(b.n), dim3(NT), 0, st, b, data, headers, w, status);
+    const int gs = (int)((L.nsub + NT - 1) / NT);
+    hipLaunchKernelGGL(jpeg_sync_spec, dim3(gs), dim3(NT), 0, st, b.n, headers, w, status);
+    for (int p = 1; p < MAX_PASSES; ++p)
+        hipLaunchKernelGGL(jpeg_sync_pass, dim3(gs), dim3(NT), 0, st, b.n, p, headers, w, status);
+    hipLaunchKernelGGL(jpeg_block_scan, dim3(b.n), dim3(NT), 0, st, b.n, w, status);
+    hipLaunchKernelGGL(jpeg_huff_write, dim3(gs), dim3(NT), 0, st, b.n, headers, w, status);
+    hipLaunchKernelGGL(jpeg_dc_scan, dim3(b.n, 3), dim3(NT), 0, st, w, status);
+    hipLaunchKernelGGL(jpeg_idct, dim3((unsigned)((g.max_blocks + NT - 1) / NT), b.n), dim3(NT), 0, st, headers, w, status);
+    hipLaunchKernelGGL(jpeg_color, dim3((unsigned)((g.max_quads + NT - 1) / NT), b.n), dim3(NT), 0, st, w, status, out);
+    return sais_check_launch();
+}
+}  // namespace
+
 extern "C" size_t sais_jpeg_workspace_bytes(int n, int height, int width, int64_t total_scan_bytes, int total_segments) {
     if (n <= 0 || height <= 0 || width <= 0 || total_scan_bytes < 0 || total_segments < n) return 0;
-    return layout_of(n, height, width, total_scan_bytes, total_segments).total;
+    return layout_of(n, height, width, total_scan_bytes, total_segments, nullptr).total;
 }
 
 extern "C" int sais_jpeg_decode(const SaisJpegBatch* batch, const unsigned char* data, const SaisJpegHeader* headers,
@@ -779,34 +871,44 @@ extern "C" int sais_jpeg_decode(const SaisJpegBatch* batch, const unsigned char*
     if (b.n <= 0 || b.height <= 0 || b.width <= 0 || b.total_scan_bytes <= 0 || b.total_segments < b.n ||
         b.data_bytes < b.total_scan_bytes)
         return SAIS_ERR_ARG;
-    const Layout L = layout_of(b.n, b.height, b.width, b.total_scan_bytes, b.total_segments);
+    Geo g{};
+    g.uniform = 1;
+    const Layout L = layout_of(b.n, b.height, b.width, b.total_scan_bytes, b.total_segments, &g.max_blocks);
     if (workspace_bytes < L.total || L.nsub >= (1LL << 31) / 2) return SAIS_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    unsigned char* ws = (unsigned char*)workspace;
-    WsPtrs w;
-    w.rec = (ImgRec*)(ws + L.rec); w.segk = (int*)(ws + L.segk); w.sego = (int*)(ws + L.sego);
-    w.sege = (int*)(ws + L.sege); w.ds = ws + L.ds; w.en = (unsigned long long*)(ws + L.en);
-    w.ex = (unsigned long long*)(ws + L.ex); w.base = (int*)(ws + L.base); w.flags = (int*)(ws + L.flags);
-    w.coef = (short*)(ws + L.coef); w.planes = ws + L.planes;
-    w.coef_blocks = L.coef_blocks; w.plane_bytes = L.plane_bytes; w.yplane = L.yplane; w.cplane = L.cplane;
-    w.nsub = L.nsub;
-    hipError_t e = hipMemsetAsync(status, 0, sizeof(int) * b.n, st);
-    if (e == hipSuccess) e = hipMemsetAsync(ws + L.ds, 0, L.en - L.ds, st);              // zero gaps between segments
-    if (e == hipSuccess) e = hipMemsetAsync(ws + L.flags, 0, L.planes - L.flags, st);    // pass flags + coefficients
-    if (e != hipSuccess) { sais_set_last_error((int)e); return SAIS_ERR_LAUNCH; }
-    hipLaunchKernelGGL(jpeg_layout, dim3(1), dim3(64), 0, st, b, headers, w, L.ds_cap, status);
-    hipLaunchKernelGGL(jpeg_destuff, dim3(b.n), dim3(NT), 0, st, b, data, headers, w, status);
-    const int gs = (int)((L.nsub + NT - 1) / NT);
-    hipLaunchKernelGGL(jpeg_sync_spec, dim3(gs), dim3(NT), 0, st, b.n, headers, w, status);
-    for (int p = 1; p < MAX_PASSES; ++p)
-        hipLaunchKernelGGL(jpeg_sync_pass, dim3(gs), dim3(NT), 0, st, b.n, p, headers, w, status);
-    hipLaunchKernelGGL(jpeg_block_scan, dim3(b.n), dim3(NT), 0, st, b.n, w, status);
-    hipLaunchKernelGGL(jpeg_huff_write, dim3(gs), dim3(NT), 0, st, b.n, headers, w, status);
-    hipLaunchKernelGGL(jpeg_dc_scan, dim3(b.n, 3), dim3(NT), 0, st, w, status);
-    hipLaunchKernelGGL(jpeg_idct, dim3((unsigned)((L.coef_blocks + NT - 1) / NT), b.n), dim3(NT), 0, st, headers, w,
-                       status);
-    const long long px = (long long)b.height * ((b.width + 3) / 4);
-    hipLaunchKernelGGL(jpeg_color, dim3((unsigned)((px + NT - 1) / NT), b.n), dim3(NT), 0, st, b.height, b.width, w,
-                       status, out);
-    return sais_check_launch();
+    g.max_quads = (long long)b.height * ((b.width + 3) / 4);
+    g.out_bytes = (long long)b.n * b.height * b.width * 3;
+    return launch_decode(b, data, headers, (unsigned char*)workspace, L, g, out, status, (hipStream_t)stream);
+}
+
+extern "C" size_t sais_jpeg_mixed_workspace_bytes(const SaisJpegHeader* headers_host, int n) {
+    if (!headers_host || n <= 0 || n > 65535) return 0;
+    const MixedSums m = mixed_sums(headers_host, n);
+    if (m.blocks == 0 || m.segments > MAX_SEGMENTS) return 0;
+    return layout_sums(n, m.scan, (int)m.segments, m.blocks, m.planes).total;
+}
+
+extern "C" int sais_jpeg_decode_mixed(int n, const unsigned char* data, int64_t data_bytes, const SaisJpegHeader* headers_host,
+                                      const SaisJpegHeader* headers_dev, const int64_t* out_offset_host,
+                                      const int64_t* out_offset_dev, void* workspace, size_t workspace_bytes, unsigned char* out,
+                                      size_t out_bytes, int* status, void* stream) {
+    SAIS_ENTER();
+    if (!data || !headers_host || !headers_dev || !out_offset_host || !out_offset_dev || !workspace || !out || !status)
+        return SAIS_ERR_ARG;
+    if (n <= 0 || n > 65535 || data_bytes <= 0 || out_bytes == 0 || out_bytes >= (1ULL << 62)) return SAIS_ERR_ARG;
+    const MixedSums m = mixed_sums(headers_host, n);
+    if (m.blocks == 0 || m.scan > data_bytes || m.segments > MAX_SEGMENTS) return SAIS_ERR_ARG;
+    for (int i = 0; i < n; ++i) {                              // the caller's offsets, on the host copy
+        ImgRec r{};
+        if (!image_geometry(headers_host[i], r)) continue;     // flagged on the device, writes nothing
+        const long long o = out_offset_host[i];
+        if (o < 0 || (unsigned long long)o + (unsigned long long)r.H * r.W * 3 > out_bytes) return SAIS_ERR_ARG;
+    }
+    const Layout L = layout_sums(n, m.scan, (int)m.segments, m.blocks, m.planes);
+    if (workspace_bytes < L.total || L.nsub >= (1LL << 31) / 2) return SAIS_ERR_ARG;
+    SaisJpegBatch b{};
+    b.n = n; b.total_segments = (int)m.segments; b.total_scan_bytes = m.scan; b.data_bytes = data_bytes;
+    Geo g{};
+    g.max_blocks = m.max_blocks; g.max_quads = m.max_quads; g.out_bytes = (long long)out_bytes;
+    g.out_off = (const long long*)out_offset_dev;
+    return launch_decode(b, data, headers_dev, (unsigned char*)workspace, L, g, out, status, (hipStream_t)stream);
 }
