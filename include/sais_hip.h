@@ -136,7 +136,9 @@ int sais_temporal_ln_bwd(const float* slabs, int nslab, long slab_stride, const 
 
 /* dW[N1,N2] += P[M,N1]^T . Q[M,N2]  and (db != NULL)  db[N1] += column sums of P.
  * Weight / bias gradients of every nn.Linear above (autograd of F.linear).  Accumulates with f32
- * atomics into dW/db (caller zeroes them: optimizer.zero_grad(), perform_training.py:155).        */
+ * atomics into dW/db (caller zeroes them: optimizer.zero_grad(), perform_training.py:155).
+ * Alignment, for this entry and the four sais_gemm_tn_* entries below: P and Q must be 16-B aligned (they are read in 16-B pieces),
+ * ldp and ldq multiples of 8 elements (4 for sais_gemm_tn_grouped_f32), dW and db 4-B aligned; N1 and N2 multiples of 128.  */
 int sais_gemm_tn(const void* P, int ldp, const void* Q, int ldq, int M, int N1, int N2,
                  float* dW, int ldw, float* db, int nsplit, void* stream);
 /* Several weight-gradient GEMMs over the same M rows in ONE launch (all bf16): the four nn.Linear of a ViT
