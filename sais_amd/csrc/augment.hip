@@ -6,12 +6,15 @@
 //                              ImagingResample on the CROPPED image (taps clamp at the box).  Every view has its own box,
 //                              so its own coefficient rows: they are computed in the kernel in double, as Resample.c
 //                              does on the host (this file is compiled with -ffp-contract=off).  One workgroup per
-//                              (view, band of output rows), horizontal pass into LDS, vertical pass out of it.
+//                              (view, band of output rows); the band itself (coefficient rows, horizontal pass into LDS,
+//                              vertical tap out of it) is resample.hpp's, shared with imgfolder.hip: the kernel here
+//                              keeps the descriptor check, the source address and the interleaved uint8 store.
 //   sais_augment_color         flip, the ColorJitter ops in the drawn order, grayscale, GaussianBlur (three box passes
 //                              per axis), solarize, ToTensor + Normalize.  One workgroup per view; the view lives in LDS
 //                              from the first op to the last and only floats are written.
 //
-// The arithmetic is restated in numpy in tests/aug_ref.py, which tests/test_augment_host.py holds against Pillow.
+// The arithmetic is restated in numpy in tests/aug_ref.py (the resampler: tests/resample_ref.py), which
+// tests/test_augment_host.py holds against Pillow.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -32,16 +35,9 @@ enum { OP_BRIGHTNESS = 0, OP_CONTRAST = 1, OP_SATURATION = 2, OP_HUE = 3, OP_GRA
 struct Border { int left, top, width, height; };
 
 // ---------------------------------------------------------------------------------------------- resampling geometry
-// (resample.hpp: Axis, make_axis, axis_coefs, band_rows_bound, clip8; every view here is bicubic)
-__host__ __device__ inline int resize_lds_bytes(int S, const Axis& ax, const Axis& ay, int band) {
-    const int ints = S * ax.ksize + 2 * S + band * ay.ksize + 2 * band;
-    return ints * 4 + ((band_rows_bound(ay, band) * S * 3 + 15) & ~15);
-}
-
+// (resample.hpp: Axis, make_axis, band_lds_bytes, pick_band, Band; every view here is bicubic and square)
 __host__ __device__ inline int pick_band(int S, const Axis& ax, const Axis& ay) {
-    for (int band = 16; band > 1; band >>= 1)
-        if (resize_lds_bytes(S, ax, ay, band) <= LDS_TARGET) return band;
-    return 1;
+    return resample::pick_band<16, LDS_TARGET, false>(S, S, ax, ay);
 }
 
 __host__ __device__ inline bool view_geometry_ok(const SaisAugView& v, int nframes, const Border& b, size_t u8_bytes) {
@@ -64,48 +60,20 @@ __global__ __launch_bounds__(RESIZE_THREADS) void crop_resize_kernel(const unsig
     const int bw = v.box[2] - v.box[0], bh = v.box[3] - v.box[1];
     const Axis ax = make_axis(bw, S), ay = make_axis(bh, S);
     const int band = pick_band(S, ax, ay);
-    if (resize_lds_bytes(S, ax, ay, band) > lds_bytes) return;
+    if (band_lds_bytes(S, ax, ay, band) > lds_bytes) return;
     const int y0 = blockIdx.y * band;
     if (y0 >= S) return;
-    const int ny = min(band, S - y0), kx = ax.ksize, ky = ay.ksize;
-    int* hk = (int*)lds;                      // [S][kx]
-    int* hb = hk + S * kx;                    // [S][2]
-    int* vk = hb + 2 * S;                     // [band][ky]
-    int* vb = vk + band * ky;                 // [band][2]
-    unsigned char* rows = (unsigned char*)(vb + 2 * band);            // [nrows][S][3]
-    for (int xx = tid; xx < S; xx += RESIZE_THREADS) axis_coefs(ax, xx, hk + xx * kx, hb[2 * xx], hb[2 * xx + 1]);
-    for (int yl = tid; yl < ny; yl += RESIZE_THREADS) axis_coefs(ay, y0 + yl, vk + yl * ky, vb[2 * yl], vb[2 * yl + 1]);
-    __syncthreads();
-    const int r0 = vb[0], nrows = vb[2 * (ny - 1)] + vb[2 * (ny - 1) + 1] - r0;
-    if (nrows > band_rows_bound(ay, band)) return;
-
-    // horizontal pass of input rows r0 .. r0+nrows-1 of the box, rounded and clipped to uint8 as Pillow stores it
-    const unsigned char* src = frames + (((size_t)v.frame * H + b.top + v.box[1] + r0) * W + b.left + v.box[0]) * 3;
-    for (int item = tid; item < nrows * S; item += RESIZE_THREADS) {
-        const int row = item / S, xx = item - row * S;
-        const int xmin = hb[2 * xx], cnt = hb[2 * xx + 1];
-        const int* k = hk + xx * kx;
-        const unsigned char* p = src + ((size_t)row * W + xmin) * 3;
-        int a0 = 1 << (PRECISION_BITS - 1), a1 = a0, a2 = a0;
-        for (int x = 0; x < cnt; ++x) {
-            const int kv = k[x];
-            a0 += p[3 * x] * kv; a1 += p[3 * x + 1] * kv; a2 += p[3 * x + 2] * kv;
-        }
-        unsigned char* t = rows + (size_t)item * 3;
-        t[0] = (unsigned char)clip8(a0); t[1] = (unsigned char)clip8(a1); t[2] = (unsigned char)clip8(a2);
-    }
-    __syncthreads();
+    const int ny = min(band, S - y0);
+    const unsigned char* box = frames + (((size_t)v.frame * H + b.top + v.box[1]) * W + b.left + v.box[0]) * 3;
+    Band<RESIZE_THREADS> bd;
+    if (!bd.fill(lds, ax, ay, S, band, 0, y0, ny, box, W, tid)) return;
 
     // vertical pass: [S][S][3] uint8, x and channel fastest
     const int line = S * 3;
     unsigned char* dst = out + v.u8_offset;
     for (int item = tid; item < ny * line; item += RESIZE_THREADS) {
         const int yl = item / line, rem = item - yl * line;
-        const int ymin = vb[2 * yl] - r0, cnt = vb[2 * yl + 1];
-        const int* k = vk + yl * ky;
-        int acc = 1 << (PRECISION_BITS - 1);
-        for (int y = 0; y < cnt; ++y) acc += rows[(size_t)(ymin + y) * line + rem] * k[y];
-        dst[(size_t)(y0 + yl) * line + rem] = (unsigned char)clip8(acc);
+        dst[(size_t)(y0 + yl) * line + rem] = (unsigned char)bd.tap(yl, rem);
     }
 }
 
@@ -333,7 +301,7 @@ extern "C" int sais_augment_crop_resize(const unsigned char* frames, int nframes
         if (!view_geometry_ok(v, nframes, b, views_u8_bytes)) return SAIS_ERR_ARG;
         const Axis ax = make_axis(v.box[2] - v.box[0], v.size), ay = make_axis(v.box[3] - v.box[1], v.size);
         const int band = pick_band(v.size, ax, ay);
-        const int need = resize_lds_bytes(v.size, ax, ay, band);
+        const int need = band_lds_bytes(v.size, ax, ay, band);
         if (need > LDS_LIMIT) return SAIS_ERR_ARG;                     // a downscale of several hundred to one
         lds = std::max(lds, need);
         max_bands = std::max(max_bands, (v.size + band - 1) / band);

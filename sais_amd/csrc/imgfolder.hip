@@ -11,9 +11,12 @@
 // computed in the kernel in double (this file is compiled with -ffp-contract=off), the horizontal pass of the input rows the
 // band needs goes to LDS as uint8 [rows][out_w][3], rounded and clipped as Pillow stores its intermediate image, and the
 // vertical pass reads it, applies the flip and the [3][256] normalisation table, and writes floats x-fastest.  There is
-// no uint8 intermediate in global memory.  The band height is chosen per image from the LDS budget.
+// no uint8 intermediate in global memory.  The band height is chosen per image from the LDS budget.  Everything up to the
+// vertical tap is resample.hpp's band (Band, band_lds_bytes, pick_band), shared with augment.hip: the kernel here keeps the
+// descriptor check, the source address and the channel-major store with flip and table.
 //
-// The arithmetic is restated in numpy in tests/imgfolder_ref.py, which tests/test_imgfolder_host.py holds against Pillow.
+// The arithmetic is restated in numpy in tests/resample_ref.py (the geometries and the table: tests/imgfolder_ref.py), which
+// tests/test_imgfolder_host.py holds against Pillow.
 #include <algorithm>
 
 #include "common.hpp"
@@ -27,18 +30,6 @@ constexpr int MAX_OUT = SAIS_IMG_MAX_OUT;
 constexpr int MAX_RESAMPLED = 1 << 20;       // rw, rh: far beyond any image, keeps every index inside int
 constexpr int LDS_TARGET = 64 * 1024;        // the tallest band that stays below this (two workgroups per CU and more)
 constexpr int LDS_LIMIT = 160 * 1024 - 3 * 256 * 4;      // dynamic part: the CU's 160 KiB less the static table
-
-__host__ __device__ inline int lds_bytes_of(int out_w, const Axis& ax, const Axis& ay, int band) {
-    const long long ints = (long long)out_w * ax.ksize + 2 * out_w + (long long)band * ay.ksize + 2 * band;
-    const long long bytes = ints * 4 + (((long long)band_rows_bound(ay, band) * out_w * 3 + 15) & ~15LL);
-    return bytes > (1 << 30) ? (1 << 30) : (int)bytes;
-}
-
-__host__ __device__ inline int pick_band(int out_h, int out_w, const Axis& ax, const Axis& ay) {
-    for (int band = 32; band > 1; band >>= 1)
-        if (band < 2 * out_h && lds_bytes_of(out_w, ax, ay, band) <= LDS_TARGET) return band;
-    return 1;
-}
 
 // everything but the LDS fit: the box, the window, the offsets
 __host__ __device__ inline bool xform_ok(const SaisImgXform& d, int out_h, int out_w, size_t src_bytes, size_t out_elems) {
@@ -59,8 +50,8 @@ __host__ __device__ inline Plan plan_of(const SaisImgXform& d, int out_h, int ou
     Plan p;
     p.ax = make_axis(d.box[2] - d.box[0], d.rw, d.filter);
     p.ay = make_axis(d.box[3] - d.box[1], d.rh, d.filter);
-    p.band = pick_band(out_h, out_w, p.ax, p.ay);
-    p.lds = lds_bytes_of(out_w, p.ax, p.ay, p.band);
+    p.band = pick_band<32, LDS_TARGET, true>(out_h, out_w, p.ax, p.ay);      // no band of twice the output height or more
+    p.lds = band_lds_bytes(out_w, p.ax, p.ay, p.band);
     return p;
 }
 
@@ -77,49 +68,18 @@ __global__ __launch_bounds__(THREADS) void image_transform_kernel(const unsigned
     const int tid = threadIdx.x, band = p.band;
     const int y0 = blockIdx.y * band;
     if (y0 >= out_h) return;
-    const int ny = min(band, out_h - y0), kx = p.ax.ksize, ky = p.ay.ksize;
-    int* hk = (int*)lds;                      // [out_w][kx]
-    int* hb = hk + out_w * kx;                // [out_w][2]
-    int* vk = hb + 2 * out_w;                 // [band][ky]
-    int* vb = vk + band * ky;                 // [band][2]
-    unsigned char* rows = (unsigned char*)(vb + 2 * band);             // [nrows][out_w][3]
-    for (int i = tid; i < 3 * 256; i += THREADS) lut[i] = lut_g[i];
-    for (int xl = tid; xl < out_w; xl += THREADS) axis_coefs(p.ax, d.win_left + xl, hk + xl * kx, hb[2 * xl], hb[2 * xl + 1]);
-    for (int yl = tid; yl < ny; yl += THREADS)
-        axis_coefs(p.ay, d.win_top + y0 + yl, vk + yl * ky, vb[2 * yl], vb[2 * yl + 1]);
-    __syncthreads();
-    const int r0 = vb[0], nrows = vb[2 * (ny - 1)] + vb[2 * (ny - 1) + 1] - r0;
-    if (nrows > band_rows_bound(p.ay, band)) return;
-
-    // horizontal pass of rows r0 .. r0+nrows-1 of the box, rounded and clipped to uint8 as Pillow stores it
-    const unsigned char* base = src + d.src_offset + (((size_t)d.box[1] + r0) * d.src_w + d.box[0]) * 3;
-    for (int item = tid; item < nrows * out_w; item += THREADS) {
-        const int row = item / out_w, xl = item - row * out_w;
-        const int xmin = hb[2 * xl], cnt = hb[2 * xl + 1];
-        const int* k = hk + xl * kx;
-        const unsigned char* q = base + ((size_t)row * d.src_w + xmin) * 3;
-        int a0 = 1 << (PRECISION_BITS - 1), a1 = a0, a2 = a0;
-        for (int x = 0; x < cnt; ++x) {
-            const int kv = k[x];
-            a0 += q[3 * x] * kv; a1 += q[3 * x + 1] * kv; a2 += q[3 * x + 2] * kv;
-        }
-        unsigned char* t = rows + (size_t)item * 3;
-        t[0] = (unsigned char)clip8(a0); t[1] = (unsigned char)clip8(a1); t[2] = (unsigned char)clip8(a2);
-    }
-    __syncthreads();
+    const int ny = min(band, out_h - y0);
+    for (int i = tid; i < 3 * 256; i += THREADS) lut[i] = lut_g[i];      // visible after the barriers of the band
+    const unsigned char* box = src + d.src_offset + ((size_t)d.box[1] * d.src_w + d.box[0]) * 3;
+    Band<THREADS> bd;
+    if (!bd.fill(lds, p.ax, p.ay, out_w, band, d.win_left, d.win_top + y0, ny, box, d.src_w, tid)) return;
 
     // vertical pass, flip, ToTensor + Normalize through the table: out[c][y][x], x fastest
-    const int line = out_w * 3;
     float* dst = out + d.out_offset;
     for (int item = tid; item < 3 * ny * out_w; item += THREADS) {
         const int c = item / (ny * out_w), rem = item - c * ny * out_w, yl = rem / out_w, x = rem - yl * out_w;
         const int xs = d.flip ? out_w - 1 - x : x;
-        const int ymin = vb[2 * yl] - r0, cnt = vb[2 * yl + 1];
-        const int* k = vk + yl * ky;
-        const unsigned char* col = rows + (size_t)ymin * line + xs * 3 + c;
-        int acc = 1 << (PRECISION_BITS - 1);
-        for (int y = 0; y < cnt; ++y) acc += col[(size_t)y * line] * k[y];
-        dst[((size_t)c * out_h + y0 + yl) * out_w + x] = lut[c * 256 + clip8(acc)];
+        dst[((size_t)c * out_h + y0 + yl) * out_w + x] = lut[c * 256 + bd.tap(yl, xs * 3 + c)];
     }
 }
 }  // namespace

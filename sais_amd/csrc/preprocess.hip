@@ -8,60 +8,40 @@
 // Integer byte work: one workgroup per (frame, band of output rows).  The horizontal pass of exactly the input
 // rows that band needs goes to LDS as uint8 [rows][224][3]; the vertical pass reads it back, and the
 // ToTensor+Normalize step is a [3][256] float table (256 possible bytes per channel: exact by construction).
-// Coefficient tables are built on the host in double, as Pillow does, once per frame geometry (a "plan").
+// Coefficient tables are built on the host in double, as Pillow does, once per frame geometry (a "plan"), from the
+// make_axis / axis_coefs of resample.hpp that the kernels of augment.hip and imgfolder.hip run on the device.  The kernel
+// here is the tuned one of the three (host tables in global memory, dword loads): it does not use that header's band.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
 #include "common.hpp"
+#include "resample.hpp"
 #include "../../include/sais_hip.h"
 
 namespace {
+using resample::PRECISION_BITS;
+using resample::clip8;
 constexpr int OUT = 224;
-constexpr int PRECISION_BITS = 32 - 8 - 2;
 constexpr int ROW_BYTES = OUT * 3;              // one horizontally-resampled row in LDS
 constexpr int LDS_BUDGET = 60 * 1024;
 
-struct Axis {
+struct AxisTable {
     std::vector<int> bounds;   // [OUT][2]  first input index, tap count
-    std::vector<int> coef;     // [OUT][ksize]
+    std::vector<int> coef;     // [OUT][ksize], zero past the tap count
     int ksize;
 };
 
-// Resample.c precompute_coeffs + normalize_coeffs_8bpc, bilinear filter, box = whole axis
-Axis make_axis(int in_size) {
-    Axis a;
-    const double scale = (double)in_size / OUT;
-    const double filterscale = scale < 1.0 ? 1.0 : scale;
-    const double support = 1.0 * filterscale;
-    a.ksize = (int)std::ceil(support) * 2 + 1;
-    const double ss = 1.0 / filterscale;
+// the coefficient rows of all OUT output indices of an axis of in_size samples (resample.hpp, bilinear), on the host
+AxisTable make_table(int in_size) {
+    const resample::Axis ax = resample::make_axis(in_size, OUT, resample::BILINEAR);
+    AxisTable a;
+    a.ksize = ax.ksize;
     a.bounds.assign(OUT * 2, 0);
     a.coef.assign((size_t)OUT * a.ksize, 0);
-    std::vector<double> w(a.ksize);
-    for (int xx = 0; xx < OUT; ++xx) {
-        const double center = 0.0 + (xx + 0.5) * scale;
-        int xmin = (int)(center - support + 0.5);
-        if (xmin < 0) xmin = 0;
-        int xmax = (int)(center + support + 0.5);
-        if (xmax > in_size) xmax = in_size;
-        xmax -= xmin;
-        double ww = 0.0;
-        for (int x = 0; x < xmax; ++x) {
-            double t = (x + xmin - center + 0.5) * ss;
-            if (t < 0.0) t = -t;
-            w[x] = t < 1.0 ? 1.0 - t : 0.0;
-            ww += w[x];
-        }
-        for (int x = 0; x < xmax; ++x) {
-            if (ww != 0.0) w[x] /= ww;
-            a.coef[(size_t)xx * a.ksize + x] =
-                w[x] < 0 ? (int)(-0.5 + w[x] * (1 << PRECISION_BITS)) : (int)(0.5 + w[x] * (1 << PRECISION_BITS));
-        }
-        a.bounds[2 * xx] = xmin;
-        a.bounds[2 * xx + 1] = xmax;
-    }
+    for (int xx = 0; xx < OUT; ++xx)
+        resample::axis_coefs(ax, xx, &a.coef[(size_t)xx * a.ksize], a.bounds[2 * xx], a.bounds[2 * xx + 1]);
     return a;
 }
 
@@ -80,11 +60,6 @@ struct Geometry {
     const int* band_rows;      // [nbands][2] first crop row, row count
     const float* lut;          // [3][256]
 };
-
-DEVINL int clip8(int acc) {
-    int v = acc >> PRECISION_BITS;
-    return v < 0 ? 0 : (v > 255 ? 255 : v);
-}
 
 DEVINL unsigned load_dword(const unsigned char* frames, long a, long total) {
     if (a + 4 <= total) return *(const unsigned*)(frames + a);
@@ -130,7 +105,9 @@ DEVINL void horizontal_pass(const Geometry& g, const unsigned char* frames, int 
     }
 }
 
-// fallback for very wide frames (more than 32 taps per column): one byte at a time
+// fallback for very wide frames (more than 32 taps per column): one byte at a time.  Its own copy of the pixel loop of
+// resample::Band::fill, to stay in step with it: behind a shared function the instructions of preprocess_kernel are scheduled
+// differently, and this kernel's machine code is kept as tuned
 DEVINL void horizontal_pass_generic(const Geometry& g, const unsigned char* frames, int f, int r0, int nrows,
                                     unsigned char* tmp, int tid) {
     for (int item = tid; item < nrows * OUT; item += 256) {
@@ -206,7 +183,7 @@ extern "C" int sais_preprocess_plan_create(int H, int W, double height_frac, dou
     const int x0 = (int)std::nearbyint((double)left), y0 = (int)std::nearbyint((double)top);
     const int x1 = (int)std::nearbyint(left + cw), y1 = (int)std::nearbyint(top + ch);
     if (x0 < 0 || y0 < 0 || x1 > W || y1 > H || x1 <= x0 || y1 <= y0) return SAIS_ERR_ARG;
-    Axis ax = make_axis(x1 - x0), ay = make_axis(y1 - y0);
+    const AxisTable ax = make_table(x1 - x0), ay = make_table(y1 - y0);
 
     // band height: the largest of 8,4,2,1 output rows whose input rows fit the LDS budget
     int band = 8, max_rows = 0;

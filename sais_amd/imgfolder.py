@@ -19,6 +19,7 @@ import torch
 
 from . import _lib as L
 from . import jpeg
+from .augment import normalize_table  # noqa: F401  (the [3][256] table of `(a / 255 - MEAN) / STD`, re-exported)
 from .knn import EvalImageFolder, eval_transform_geometry, list_image_folder
 from .linear import TrainImageFolder
 
@@ -27,13 +28,6 @@ XFORM_DTYPE = np.dtype([("src_offset", "<i8"), ("src_h", "<i4"), ("src_w", "<i4"
                         ("rh", "<i4"), ("win_left", "<i4"), ("win_top", "<i4"), ("filter", "<i4"), ("flip", "<i4"),
                         ("out_offset", "<i8")], align=True)
 assert XFORM_DTYPE.itemsize == ctypes.sizeof(L.SaisImgXform)
-
-
-def normalize_table():
-    """[3][256] float32: what the datasets' `(a / 255 - MEAN) / STD` gives each byte of each channel (the table of
-    augment.normalize_table)."""
-    from .augment import normalize_table as table
-    return table()
 
 
 # ------------------------------------------------------------------------------------------------ worker-side datasets
@@ -212,8 +206,6 @@ class _HipBackend:
         self._lut = torch.from_numpy(normalize_table()).to(self.device)
         self._pinned = self._dev = self._ws = self._status = None
 
-    _grow = staticmethod(jpeg.JpegDecoder._grow)
-
     def decode(self, plan):
         """Pack, copy, decode: the status of plan.gpu (numpy int32), after which the pinned buffer is free again."""
         al = lambda v: (v + 255) // 256 * 256                        # noqa: E731
@@ -238,8 +230,8 @@ class _HipBackend:
             dec_off.append(o - upload)
             o = al(o + 3 * w * h)
         total = o
-        self._pinned = self._grow(self._pinned, upload, pin_memory=True)
-        self._dev = self._grow(self._dev, total, device=self.device)
+        self._pinned = jpeg.grow(self._pinned, upload, pin_memory=True)
+        self._dev = jpeg.grow(self._dev, total, device=self.device)
         base = self._pinned.data_ptr()
         pin = self._pinned.numpy()
         headers = (jpeg.SaisJpegHeader * max(m, 1))()
@@ -268,7 +260,7 @@ class _HipBackend:
                 need = lib.sais_jpeg_mixed_workspace_bytes(headers, m)
                 if need == 0:
                     raise L.SaisHipError("sais_jpeg_mixed_workspace_bytes rejected the batch")
-                self._ws = self._grow(self._ws, need, device=self.device)
+                self._ws = jpeg.grow(self._ws, need, device=self.device)
                 if self._status is None or self._status.numel() < m:
                     self._status = torch.empty(max(m, 256), dtype=torch.int32, device=self.device)
                 d = self._dev.data_ptr()

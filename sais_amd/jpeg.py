@@ -63,6 +63,14 @@ def _host_decode(blob):
         return np.asarray(img)
 
 
+def grow(buf, nbytes, **kw):
+    """A reused uint8 buffer of at least nbytes: `buf` itself, or a new one of at least twice its size (the decoder's, the
+    encoder's and the image-folder loader's pinned, device and workspace buffers)."""
+    if buf is None or buf.numel() < nbytes:
+        buf = torch.empty(max(nbytes, 2 * (0 if buf is None else buf.numel())), dtype=torch.uint8, **kw)
+    return buf
+
+
 class JpegDecoder:
     """Decodes batches of one geometry.  The compressed bytes and the per-image headers go to the device in one copy
     from a reused pinned buffer; the workspace is reused too.  stats counts the files per path."""
@@ -74,12 +82,6 @@ class JpegDecoder:
         L.load()
         self._pinned = self._dev = self._ws = self._status = None
         self.stats = {"gpu": 0, "unsupported": 0, "failed": 0}
-
-    @staticmethod
-    def _grow(buf, nbytes, **kw):
-        if buf is None or buf.numel() < nbytes:
-            buf = torch.empty(max(nbytes, 2 * (0 if buf is None else buf.numel())), dtype=torch.uint8, **kw)
-        return buf
 
     def decode(self, blobs, headers=None):
         """blobs: list of JPEG file contents of one geometry -> uint8 [N,H,W,3] on the device.
@@ -121,8 +123,8 @@ class JpegDecoder:
             offs.append(o)
             o += len(b)
         total = data_off + o
-        self._pinned = self._grow(self._pinned, total, pin_memory=True)
-        self._dev = self._grow(self._dev, total, device=self.device)
+        self._pinned = grow(self._pinned, total, pin_memory=True)
+        self._dev = grow(self._dev, total, device=self.device)
         base = self._pinned.data_ptr()
         for k, (b, h) in enumerate(zip(blobs, headers)):
             hh = SaisJpegHeader.from_buffer_copy(h)
@@ -134,7 +136,7 @@ class JpegDecoder:
         need = lib.sais_jpeg_workspace_bytes(m, H, W, bt.total_scan_bytes, bt.total_segments)
         if need == 0:
             raise L.SaisHipError("sais_jpeg_workspace_bytes rejected the batch")
-        self._ws = self._grow(self._ws, need, device=self.device)
+        self._ws = grow(self._ws, need, device=self.device)
         if self._status is None or self._status.numel() < m:
             self._status = torch.empty(max(m, 256), dtype=torch.int32, device=self.device)
         dst = out if m == out.shape[0] else torch.empty(m, H, W, 3, dtype=torch.uint8, device=self.device)

@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .jpeg import grow
 
 # ITU-T T.81 Annex K: quantisation tables (natural order) and Huffman tables (code counts per length 1..16, symbols)
 Q_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
@@ -117,12 +118,6 @@ class JpegEncoder:
         L.load()
         self._ws = self._out = self._nbytes = self._pinned = None
 
-    @staticmethod
-    def _grow(buf, nbytes, **kw):
-        if buf is None or buf.numel() < nbytes:
-            buf = torch.empty(max(nbytes, 2 * (0 if buf is None else buf.numel())), dtype=torch.uint8, **kw)
-        return buf
-
     def _check(self, rgb):
         if not isinstance(rgb, torch.Tensor) or rgb.device != self.device or rgb.dtype != torch.uint8 or rgb.dim() != 4 \
                 or rgb.shape[3] != 3 or rgb.shape[0] < 1 or not rgb.is_contiguous():
@@ -157,9 +152,9 @@ class JpegEncoder:
         for t, table in enumerate(quant_tables(quality)):
             for k in range(64):
                 p.q[t][k] = int(table[k])
-        self._ws = self._grow(self._ws, need, device=self.device)
+        self._ws = grow(self._ws, need, device=self.device)
         if out is None:
-            self._out = self._grow(self._out, n * stride, device=self.device)
+            self._out = grow(self._out, n * stride, device=self.device)
             out = self._out[:n * stride].view(n, stride)
         if self._nbytes is None or self._nbytes.numel() < n:
             self._nbytes = torch.empty(max(n, 256), dtype=torch.int32, device=self.device)
@@ -177,7 +172,7 @@ class JpegEncoder:
         if (lens < 2).any():
             raise L.SaisHipError(f"sais_jpeg_encode: image {int(np.flatnonzero(lens < 2)[0])} did not fit its worst-case bound")
         longest = int(lens.max())
-        self._pinned = self._grow(self._pinned, n * longest, pin_memory=True)
+        self._pinned = grow(self._pinned, n * longest, pin_memory=True)
         host = self._pinned[:n * longest].view(n, longest)
         host.copy_(out[:, :longest])                                      # copy 2: the used bytes
         rows = host.numpy()

@@ -2,72 +2,20 @@
 array out).  tests/test_augment_host.py holds every function here against Pillow bit for bit; the kernels of
 sais_amd/csrc/augment.hip implement exactly this arithmetic.
 
-Source of each: Pillow's Resample.c (8-bit ImagingResample, bicubic), Convert.c (rgb2l, rgb2hsv, hsv2rgb), Blend.c
+Source of each: Pillow's Resample.c (8-bit ImagingResample, bicubic: tests/resample_ref.py), Convert.c (rgb2l, rgb2hsv, hsv2rgb), Blend.c
 (ImageEnhance = Image.blend(degenerate, image, factor)), BoxBlur.c (GaussianBlur = three box passes per axis),
 ImageOps.solarize."""
 import numpy as np
 
-PRECISION_BITS = 32 - 8 - 2
+from resample_ref import BICUBIC, window_u8
+
 f32 = np.float32
 
 
 # ------------------------------------------------------------------ crop + bicubic resize
-def bicubic(x, a=-0.5):
-    x = abs(x)
-    if x < 1.0:
-        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
-    if x < 2.0:
-        return (((x - 5) * x + 8) * x - 4) * a
-    return 0.0
-
-
-def coefficients(in_size, out_size):
-    """precompute_coeffs + normalize_coeffs_8bpc for a box that is the whole (already cropped) axis:
-    (bounds [out][2] = first input index, tap count; coef [out][ksize] int32)."""
-    scale = in_size / out_size
-    fs = max(scale, 1.0)
-    support = 2.0 * fs
-    ksize = int(np.ceil(support)) * 2 + 1
-    ss = 1.0 / fs
-    bounds = np.zeros((out_size, 2), np.int64)
-    coef = np.zeros((out_size, ksize), np.int64)
-    for xx in range(out_size):
-        c = (xx + 0.5) * scale
-        xmin = max(int(c - support + 0.5), 0)
-        xmax = min(int(c + support + 0.5), in_size) - xmin
-        w = [bicubic((x + xmin - c + 0.5) * ss) for x in range(xmax)]
-        ww = 0.0
-        for v in w:
-            ww += v
-        for x in range(xmax):
-            v = w[x] / ww if ww != 0.0 else w[x]
-            coef[xx, x] = int(v * (1 << PRECISION_BITS) - 0.5) if v < 0 else int(v * (1 << PRECISION_BITS) + 0.5)
-        bounds[xx] = xmin, xmax
-    return bounds, coef
-
-
-def _resample_axis0(a, out_size):
-    """a: uint8 [in, ...] -> uint8 [out, ...] along axis 0."""
-    bounds, coef = coefficients(a.shape[0], out_size)
-    out = np.empty((out_size,) + a.shape[1:], np.uint8)
-    a = a.astype(np.int64)
-    for xx in range(out_size):
-        lo, n = bounds[xx]
-        k = coef[xx, :n].reshape((n,) + (1,) * (a.ndim - 1))
-        acc = (a[lo:lo + n] * k).sum(0) + (1 << (PRECISION_BITS - 1))
-        out[xx] = np.clip(acc >> PRECISION_BITS, 0, 255)
-    return out
-
-
 def crop_resize(frame, box, size):
     """img.crop(box).resize((size, size), Image.BICUBIC) of a uint8 [H,W,3] frame; box = left, top, right, bottom."""
-    l, t, r, b = box
-    a = frame[t:b, l:r]
-    if a.shape[1] != size:                                           # Pillow skips a pass that changes nothing
-        a = _resample_axis0(a.transpose(1, 0, 2), size).transpose(1, 0, 2)     # horizontal first, rounded to uint8
-    if a.shape[0] != size:
-        a = _resample_axis0(a, size)
-    return np.ascontiguousarray(a)
+    return window_u8(frame, box, size, size, 0, 0, size, size, BICUBIC)
 
 
 # ------------------------------------------------------------------ pointwise colour operations

@@ -73,8 +73,9 @@ def test_mixed_decode_matches_pillow_and_the_uniform_decoder():
 
 
 # ------------------------------------------------------------------------------------------------ transform on raw arrays
-def _run_transform(images, geometries, out_hw, order=None):
-    """One sais_image_transform launch over raw uint8 arrays; image i writes output slot order[i].  -> float32 [n,3,h,w]."""
+def _run_transform(images, geometries, out_hw, order=None, lut=None):
+    """One sais_image_transform launch over raw uint8 arrays; image i writes output slot order[i].  -> float32 [n,3,h,w].
+    lut: a [3][256] float32 table in place of the normalisation table."""
     from sais_amd import _lib as L, imgfolder
     oh, ow = out_hw
     n = len(images)
@@ -89,12 +90,36 @@ def _run_transform(images, geometries, out_hw, order=None):
         src[row[0]:row[0] + img.size] = img.reshape(-1)
     src_d = torch.from_numpy(src).to(DEV)
     table_d = torch.from_numpy(table.view(np.uint8).reshape(-1).copy()).to(DEV)
-    lut = torch.from_numpy(imgfolder.normalize_table()).to(DEV)
+    lut = torch.from_numpy(imgfolder.normalize_table() if lut is None else lut).to(DEV)
     out = torch.full((n, 3, oh, ow), float("nan"), dtype=torch.float32, device=DEV)
     L.call("sais_image_transform", src_d.data_ptr(), src_d.numel(), table.ctypes.data, table_d.data_ptr(), n, oh, ow,
            lut.data_ptr(), out.data_ptr(), out.numel(), torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     return out.cpu()
+
+
+@gpu
+def test_crop_resize_and_image_transform_share_one_resampler():
+    """The two kernels built on the band of resample.hpp give the same bytes, and those of the numpy restatement.  S = 17 ends
+    crop_resize's second band (16 rows) after one row while image_transform takes it in one band; S = 33 ends the last band
+    of both after one row (bands of 16 and 32); S = 96 is 6 and 3 full bands, once upscaling from 3 x 2 pixels; S = 1 is a
+    single output byte."""
+    from sais_amd.augment import DinoAugmenter
+    from sais_amd.dino_data import ViewParams
+    img = R.make_image(131, 97)
+    frames = torch.from_numpy(img[None]).to(DEV)
+    aug = DinoAugmenter(DEV)
+    identity = np.ascontiguousarray(np.broadcast_to(np.arange(256, dtype=np.float32), (3, 256)))
+    for box, s in [((0, 0, 131, 97), 1), ((0, 0, 131, 97), 17), ((2, 1, 130, 96), 33), ((5, 5, 45, 35), 96), ((0, 0, 3, 2), 96)]:
+        view = ViewParams(box=box, size=s, flip=False, jitter=False, order=(0, 1, 2, 3), brightness=1.0, contrast=1.0,
+                          saturation=1.0, hue=0.0, gray=False, blur=None, solarize=False)
+        cropped = aug.crop_resize(frames, [[view]], (0, 0, 131, 97))[0][0].cpu()
+        out = _run_transform([img], [(box, (s, s), (0, 0), R.BICUBIC, False)], (s, s), lut=identity)[0]
+        assert tuple(cropped.shape) == (s, s, 3) and cropped.dtype == torch.uint8
+        assert torch.equal(out.to(torch.uint8).permute(1, 2, 0), cropped), (box, s)
+        assert torch.equal(out, out.to(torch.uint8).to(torch.float32)), (box, s)         # whole bytes: the cast dropped nothing
+        want = torch.from_numpy(R.window_u8(img, box, s, s, 0, 0, s, s, R.BICUBIC))
+        assert torch.equal(cropped, want), (box, s)
 
 
 @gpu
