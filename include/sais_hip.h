@@ -713,7 +713,8 @@ int sais_importance_bwd(const float* dlogit /*[M]*/, const float* z, const float
                         float* db, void* stream);
 /* calcImportanceLoss, prepare_miscellaneous.py:48-60 (quirks kept: scalar mean BCE broadcast against the inverted
  * mask with its last entry dropped; mean over label-0 samples, NaN if none).  logits [B,T+1] (slot 0 = CLS),
- * target [B,T], ipad [B,T+1] (1 = masked).  dlogits (optional) [B,T+1] = scale * d loss / d logits.           */
+ * target [B,T], ipad [B,T+1] (1 = masked).  dlogits (optional) [B,T+1] = scale * d loss / d logits; with no
+ * label-0 sample the loss is NaN and dlogits is exactly 0, as autograd of the mean over an empty selection gives. */
 int sais_importance_loss(const float* logits, const float* target, const unsigned char* ipad, const int* labels,
                          int B, int T, float* loss, float* dlogits, float scale, void* stream);
 

@@ -258,12 +258,12 @@ __global__ __launch_bounds__(384) void importance_bwd_kernel(const float* dl, co
 
 // calcImportanceLoss (prepare_miscellaneous.py:48-60), quirks kept; one workgroup.  logits [B,S] (slot 0 = CLS),
 // target [B,T], ipad [B,S] (1 = masked), labels [B].  loss = mean_bce * sum_{b low, t<T} !ipad[b,t] / (nlow T);
-// dlogits[b,1+t] = frac * (sigmoid(x) - target) / (B T) * scale, dlogits[b,0] = 0.
+// dlogits[b,1+t] = frac * (sigmoid(x) - target) / (B T) * scale, dlogits[b,0] = 0; all of dlogits = 0 when nlow = 0.
 __global__ __launch_bounds__(256) void importance_loss_kernel(const float* logits, const float* target,
                                                               const unsigned char* ipad, const int* labels, int B, int T,
                                                               float* loss, float* dlogits, float scale) {
     __shared__ float red[256];
-    __shared__ float s_frac, s_bce;
+    __shared__ float s_frac, s_bce, s_k;
     const int S = T + 1, tid = threadIdx.x;
     float a = 0.f, cnt = 0.f, nlow = 0.f;
     for (int i = tid; i < B * T; i += 256) {
@@ -284,10 +284,13 @@ __global__ __launch_bounds__(256) void importance_loss_kernel(const float* logit
         s_bce = a / (float)(B * T);
         s_frac = cnt / (nlow * (float)T);          // 0/0 = NaN when no low-skill sample: torch.mean of an empty tensor
         if (loss) *loss = s_bce * s_frac;
+        // no low-skill sample: the loss is NaN but autograd of the mean over an empty selection scatters nothing back, so the
+        // gradient is exactly 0 (NaN here would reach every weight of the step)
+        s_k = nlow > 0.f ? s_frac * scale / (float)(B * T) : 0.f;
     }
     __syncthreads();
     if (!dlogits) return;
-    const float k = s_frac * scale / (float)(B * T);
+    const float k = s_k;
     for (int i = tid; i < B * S; i += 256) {
         const int b = i / S, s = i - b * S;
         float g = 0.f;
