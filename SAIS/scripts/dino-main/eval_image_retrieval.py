@@ -14,7 +14,10 @@ Differences: only `--arch vit_small` with `--patch_size 16` or `8` (anything els
 the weights stay random and the script says so (no download of the Google-Landmarks checkpoint); one process (WORLD_SIZE > 1
 exits, as eval_knn.py here); `--dist_url` / `--local_rank` / `--use_cuda` are accepted and ignored; sides that are no multiple of
 16 are cropped at the right and bottom to the multiple below, which is what the reference's patch embedding computes; equal
-similarities rank in ascending database index; `--dump_features <dir>` (new) saves the normalised features.
+similarities rank in ascending database index; `--dump_features <dir>` (new) saves the normalised features;
+`--gpu_loader true` (new) decodes the files and makes the thumbnails on the GPU (sais_amd/imgfolder.py: the workers only read
+the files, `--gpu_loader_batch` of them per decode call), bit-identical to the Pillow loader's, and `--group_shapes true` (new,
+with `--gpu_loader true` only) hands the thumbnails of one such batch that share a shape to the backbone together.
 """
 import argparse
 import os
@@ -24,7 +27,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", ".."))
-from sais_amd import retrieval  # noqa: E402
+from sais_amd import imgfolder, retrieval  # noqa: E402
 from sais_amd.model_io import bool_flag, load_dino_backbone  # noqa: E402
 
 
@@ -45,11 +48,22 @@ def get_args_parser():
     parser.add_argument("--dist_url", default="env://", type=str, help="Accepted and ignored.")
     parser.add_argument("--local_rank", default=0, type=int, help="Accepted and ignored.")
     parser.add_argument('--dump_features', default=None, help='Directory for trainfeat.pth / queryfeat.pth (normalised features)')
+    parser.add_argument('--gpu_loader', default=False, type=bool_flag,
+                        help="""Decode the images and make the thumbnails on the GPU (sais_amd/imgfolder.py): the workers only
+        read the files.  The images are bit-identical to the Pillow loader's.""")
+    parser.add_argument('--gpu_loader_batch', default=64, type=int, help='Files per decode call of --gpu_loader.')
+    parser.add_argument('--group_shapes', default=False, type=bool_flag,
+                        help="""With --gpu_loader true: thumbnails of one loader batch that share a shape go through the
+        backbone together instead of one by one.""")
     return parser
 
 
 def main(argv=None):
     args = get_args_parser().parse_args(argv)
+    if args.group_shapes and not args.gpu_loader:
+        sys.exit("--group_shapes true needs --gpu_loader true: the Pillow loader yields one image per batch")
+    if args.gpu_loader_batch < 1:
+        sys.exit("--gpu_loader_batch must be at least 1")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         sys.exit("eval_image_retrieval.py runs as one process on one GPU: multi-rank feature extraction is not implemented "
                  "(start it without a distributed launcher)")
@@ -60,10 +74,18 @@ def main(argv=None):
     dev = torch.device("cuda:0")
 
     # ============ preparing data ... ============
-    dataset_train = retrieval.OxfordParisDataset(args.data_path, args.dataset, split="train", imsize=args.imsize)
-    dataset_query = retrieval.OxfordParisDataset(args.data_path, args.dataset, split="query", imsize=args.imsize)
-    loader = lambda ds: torch.utils.data.DataLoader(ds, batch_size=1, num_workers=args.num_workers, pin_memory=True,
-                                                    drop_last=False, shuffle=False)
+    if args.gpu_loader:
+        gpu_loader = imgfolder.GpuImageLoader(dev)
+        dataset_train = imgfolder.RawOxfordParis(args.data_path, args.dataset, split="train")
+        dataset_query = imgfolder.RawOxfordParis(args.data_path, args.dataset, split="query")
+        loader = lambda ds: retrieval.ThumbnailBatches(torch.utils.data.DataLoader(
+            ds, batch_size=args.gpu_loader_batch, num_workers=args.num_workers, drop_last=False, shuffle=False,
+            collate_fn=imgfolder.collate_raw), gpu_loader, args.imsize, args.group_shapes)
+    else:
+        dataset_train = retrieval.OxfordParisDataset(args.data_path, args.dataset, split="train", imsize=args.imsize)
+        dataset_query = retrieval.OxfordParisDataset(args.data_path, args.dataset, split="query", imsize=args.imsize)
+        loader = lambda ds: torch.utils.data.DataLoader(ds, batch_size=1, num_workers=args.num_workers, pin_memory=True,
+                                                        drop_last=False, shuffle=False)
     print(f"train: {len(dataset_train)} imgs / query: {len(dataset_query)} imgs")
 
     # ============ building network ... ============
@@ -75,6 +97,8 @@ def main(argv=None):
     # Step 1: extract features, normalize
     train_features = retrieval.l2_normalize(retrieval.extract_features(fn, loader(dataset_train), dev))
     query_features = retrieval.l2_normalize(retrieval.extract_features(fn, loader(dataset_query), dev))
+    if args.gpu_loader:
+        print("gpu loader:", gpu_loader.stats)
     if args.dump_features:
         os.makedirs(args.dump_features, exist_ok=True)
         torch.save(train_features.cpu(), os.path.join(args.dump_features, "trainfeat.pth"))

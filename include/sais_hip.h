@@ -633,6 +633,55 @@ int    sais_image_transform(const unsigned char* src, size_t src_bytes, const Sa
                             const SaisImgXform* table_dev, int n, int out_h, int out_w, const float* lut, float* out,
                             size_t out_elems, void* stream);
 
+/* ---------------------------------------------------------------- thumbnail(LANCZOS) of the retrieval loader (csrc/thumbnail.hip)
+ * retrieval.OxfordParisDataset: Image.open(fh).convert("RGB"), img.thumbnail((imsize, imsize), Image.LANCZOS), ToTensor +
+ * Normalize, on decoded images of any size packed in one uint8 buffer.  Additive entries: the ABI version does not change.
+ * After convert() the image is a plain Image, so Image.thumbnail (Pillow 12.2) uses no JPEG draft mode; it is
+ *   (x, y) = the aspect-preserving size (Image.thumbnail, round_aspect); not larger than the image: left untouched
+ *   fx = int(W / x / 2.0) or 1, fy = int(H / y / 2.0) or 1          (Image.resize, reducing_gap = 2.0)
+ *   img.reduce((fx, fy)) where a factor exceeds 1                    (Image.reduce / Reduce.c: box average, rw x rh =
+ *                                                                     ceil(W / fx) x ceil(H / fy), last column / row partial)
+ *   resize((x, y), LANCZOS, box = (0, 0, W / fx, H / fy))            (Resample.c: precompute_coeffs with lanczos_filter,
+ *                                                                     normalize_coeffs_8bpc, ImagingResampleInner; the box
+ *                                                                     ends are C floats: _imaging.c parses "(ffff)")
+ * Image.resize ends with a branch for tall, narrow images: where the reduced image has rh > 100 * rw and out_h < rh, the vertical
+ * pass runs first, as a resize of its own.  These entries run the horizontal pass first, so they REFUSE that geometry
+ * (SAIS_ERR_ARG; sais_thumbnail_fits answers 0) and a caller routes such an image to Pillow.
+ * Image i -> float32 [3, out_h, out_w] at out + out_offset (elements) through `lut` (device float [3][256]), bit-identical.
+ * lanczos_filter is sinc(x) * sinc(x / 3) from the C library's sin in double; no kernel evaluates it.  sais_lanczos_rows, a
+ * host function, writes the rows of one axis: bounds int [out][2] (first input index, taps) and coefs int [out][ksize] for
+ * `src_size` samples reduced by `factor` and resampled to `out_size`.  It returns ksize; 0 where Pillow skips the pass (same
+ * size, whole box: nothing is written); with bounds = coefs = NULL it only answers ksize.  In the coefficient buffer of
+ * sais_thumbnail the rows of an axis lie at c?_offset (ints) as [out][2] bounds followed by [out][k?] coefficients; k? = 0
+ * says the pass is skipped (the side must then equal the reduced side; both 0 with factors 1: a normalised copy).
+ * The table and the coefficient buffer are passed twice, as the augment entries take their table: the host copies are checked
+ * (every tap inside the reduced image, every band within its LDS rows), the device copies are read.  SAIS_ERR_ARG and nothing
+ * launched for n outside 1..65535, output sides outside 1..SAIS_THUMB_MAX_OUT, source sides above 65535 or more than 2^28
+ * pixels, a factor below 1 or fx * fy above 65536, rw / rh that are not the reduced size, the vertical-first geometry above, an offset outside a buffer, or a
+ * one-row band that does not fit in LDS (sais_thumbnail_fits, a host function, answers 0 for a geometry that is refused, so a
+ * caller can route it elsewhere first).  SAIS_THUMB_MAX_OUT is 1024: the coefficient rows stay in global memory, LDS holds
+ * only the horizontally resampled rows of a band ((2 + ky) * out_w * 3 bytes for a one-row band, 83 KiB at 1024 and ky = 25).
+ * The workspace holds the reduced images at ws_offset (bytes, chosen by the caller; unused with factors 1);
+ * sais_thumbnail_workspace_bytes answers the bytes a table needs (0: a refused table). */
+#define SAIS_THUMB_MAX_OUT 1024
+typedef struct SaisThumb {
+    int64_t src_offset;              /* bytes, into src: the image is uint8 [src_h, src_w, 3]                  */
+    int src_h, src_w;
+    int fx, fy;                      /* Image.reduce factors, >= 1                                             */
+    int rw, rh;                      /* ceil(src_w / fx), ceil(src_h / fy)                                     */
+    int64_t ws_offset;               /* bytes, into ws: the reduced image uint8 [rh, rw, 3]                    */
+    int out_w, out_h;
+    int kx, ky;                      /* taps per coefficient row; 0 = the pass is skipped                      */
+    int64_t cx_offset, cy_offset;    /* ints, into coef                                                        */
+    int64_t out_offset;              /* float elements, into out                                               */
+} SaisThumb;
+int    sais_lanczos_rows(int src_size, int factor, int out_size, int* bounds, int* coefs, int ksize);
+int    sais_thumbnail_fits(const SaisThumb* d);
+size_t sais_thumbnail_workspace_bytes(const SaisThumb* table_host, int n);
+int    sais_thumbnail(const unsigned char* src, size_t src_bytes, const SaisThumb* table_host, const SaisThumb* table_dev, int n,
+                      const int* coef_host, const int* coef_dev, size_t coef_ints, unsigned char* ws, size_t ws_bytes,
+                      const float* lut, float* out, size_t out_elems, void* stream);
+
 /* ---------------------------------------------------------------- temporal encoder glue (dim 384, 4 heads x 96)
  * prepareInputForTransformer, prepare_model.py:179-195: z[b,0] = frame_cls, z[b,1+t] = x[b,t] + pos[t]
  * (out of place: the reference's in-place += on the caller's tensor is NOT reproduced).          */

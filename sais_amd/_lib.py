@@ -101,6 +101,15 @@ class SaisAugView(ctypes.Structure):
                 ("reserved", c_int), ("u8_offset", ctypes.c_int64), ("out_offset", ctypes.c_int64)]
 
 
+THUMB_MAX_OUT = 1024                                   # SAIS_THUMB_MAX_OUT
+
+
+class SaisThumb(ctypes.Structure):
+    _fields_ = [("src_offset", ctypes.c_int64), ("src_h", c_int), ("src_w", c_int), ("fx", c_int), ("fy", c_int), ("rw", c_int),
+                ("rh", c_int), ("ws_offset", ctypes.c_int64), ("out_w", c_int), ("out_h", c_int), ("kx", c_int), ("ky", c_int),
+                ("cx_offset", ctypes.c_int64), ("cy_offset", ctypes.c_int64), ("out_offset", ctypes.c_int64)]
+
+
 class SaisImgXform(ctypes.Structure):
     _fields_ = [("src_offset", ctypes.c_int64), ("src_h", c_int), ("src_w", c_int), ("box", c_int * 4), ("rw", c_int),
                 ("rh", c_int), ("win_left", c_int), ("win_top", c_int), ("filter", c_int), ("flip", c_int),
@@ -212,6 +221,12 @@ SIGNATURES = {
     "sais_image_transform_fits": [c_void_p, c_int, c_int],
     "sais_image_transform": [c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                              ctypes.c_size_t, c_void_p],
+    # thumbnail(LANCZOS) of the retrieval loader (csrc/thumbnail.hip)
+    "sais_lanczos_rows": [c_int, c_int, c_int, c_void_p, c_void_p, c_int],
+    "sais_thumbnail_fits": [c_void_p],
+    "sais_thumbnail_workspace_bytes": [c_void_p, c_int],
+    "sais_thumbnail": [c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_int, c_void_p, c_void_p, ctypes.c_size_t, c_void_p,
+                       ctypes.c_size_t, c_void_p, c_void_p, ctypes.c_size_t, c_void_p],
     "sais_scale_f32": [c_void_p, c_long, c_float, c_void_p],
     "sais_touch": [c_void_p, c_long, c_void_p],
     "sais_temporal_prepare_fwd": [c_void_p, c_long, c_long, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
@@ -325,6 +340,7 @@ def load():
     lib.sais_jpeg_encode_bound.restype = ctypes.c_size_t
     lib.sais_jpeg_encode_workspace_bytes.restype = ctypes.c_size_t
     lib.sais_augment_workspace_bytes.restype = ctypes.c_size_t
+    lib.sais_thumbnail_workspace_bytes.restype = ctypes.c_size_t
     lib.sais_gemm_tn_grouped_slab_bytes.restype = ctypes.c_size_t
     lib.sais_knn_workspace_bytes.restype = ctypes.c_size_t
     lib.sais_colmean_cov_workspace_bytes.restype = ctypes.c_size_t

@@ -400,6 +400,37 @@ class OxfordParisDataset(torch.utils.data.Dataset):
         return _to_tensor(img), index
 
 
+class ThumbnailBatches:
+    """OxfordParisDataset's loader with the pixels made on the GPU: wraps a DataLoader over imgfolder.RawOxfordParis
+    (collate_raw) and a GpuImageLoader, and yields what extract_features takes.  Per image (the default): (samples
+    [1, 3, h, w], index [1]) in dataset order, as the Pillow loader at batch size 1 yields them, bit for bit.  With
+    group_shapes the thumbnails of one loader batch that share a shape are stacked: ([F, 3, h, w], index [F]), groups in
+    the order of their first image; extract_features scatters the rows by index.  A backbone call on F frames computes
+    each row as it computes it alone up to the rounding of its kernels' batch-dependent tiling; under multi_scale the
+    result is also divided by the norm of the WHOLE batch tensor, a scalar per call that the row normalisation after
+    extract_features (l2_normalize) removes up to rounding."""
+
+    def __init__(self, loader, gpu_loader, imsize, group_shapes=False):
+        self.loader, self.gpu_loader, self.imsize, self.group_shapes = loader, gpu_loader, int(imsize), bool(group_shapes)
+        self.dataset = loader.dataset
+
+    def __len__(self):
+        return len(self.loader)
+
+    def __iter__(self):
+        for items, tags in self.loader:
+            thumbs = self.gpu_loader.thumbnail(items, self.imsize)
+            if not self.group_shapes:
+                for k, t in enumerate(thumbs):
+                    yield t, tags[k:k + 1]
+                continue
+            groups = {}
+            for k, t in enumerate(thumbs):
+                groups.setdefault(tuple(t.shape[2:]), []).append(k)
+            for ks in groups.values():
+                yield torch.cat([thumbs[k] for k in ks]), tags[ks]
+
+
 @torch.no_grad()
 def extract_features(fn, loader, device="cuda:0"):
     """Features [N, D] on the device in dataset order; `loader` yields (images, dataset indices), fn maps device frames to [F, D]
