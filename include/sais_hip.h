@@ -704,6 +704,21 @@ int sais_temporal_attn_fwd(const float* qkv /*[B*S,1152]*/, const unsigned char*
 int sais_temporal_attn_bwd(const float* qkv, const unsigned char* key_pad, int B, int S, const float* dctx, int nslab,
                            long slab_stride, float* dqkv /*[B*S,1152]*/, float p_drop, const unsigned long long* rng_state,
                            unsigned site, void* stream);
+/* The same attention for 1 <= S <= SAIS_TEMPORAL_LONG_MAX_S (the 2000-row position table + CLS; csrc/tattn_long.hip): keys and
+ * values stream through LDS in 64-row tiles, a workgroup owns 64 queries.  Same arguments, same mask element index (in 64 bits),
+ * same Philox state.  attn_avg needs NO pre-zeroing and is bit-reproducible (fixed-order head sum), as are ctx and dqkv.  The
+ * backward takes a workspace of sais_temporal_attn_long_bwd_workspace_bytes(B, S) bytes, 16-B aligned (the slab sum of dctx and
+ * the row statistics its first launch leaves for the second); no float atomics.  SAIS_ERR_ARG and nothing launched for S out
+ * of range, B > 65535, p_drop outside [0, 1), p_drop > 0 without rng_state, slab_stride & 3, or a workspace too small.
+ * sais_temporal_layer_fwd / _bwd use these for S > SAIS_TEMPORAL_MAX_S_FWD and the resident kernels up to it. */
+#define SAIS_TEMPORAL_LONG_MAX_S 2001
+size_t sais_temporal_attn_long_bwd_workspace_bytes(int B, int S);
+int sais_temporal_attn_fwd_long(const float* qkv, const unsigned char* key_pad, int B, int S, float* ctx,
+                                float* attn_avg /*optional [B,S,S]*/, float p_drop, const unsigned long long* rng_state,
+                                unsigned site, void* stream);
+int sais_temporal_attn_bwd_long(const float* qkv, const unsigned char* key_pad, int B, int S, const float* dctx, int nslab,
+                                long slab_stride, float* dqkv, float p_drop, const unsigned long long* rng_state, unsigned site,
+                                void* workspace, size_t workspace_bytes, void* stream);
 /* Train mode (model.train(), train.py:59): nn.TransformerEncoderLayer's default dropout = 0.1 (prepare_model.py:75) acts at
  * four sites per layer: on the attention weights (p_drop above: after the softmax, before P v; the returned map is the
  * dropped one, as in torch 1.8), after out_proj (dropout1), after the ReLU (dropout) and after linear2 (dropout2).

@@ -145,6 +145,8 @@ EPI_BIAS_RELU_F32, EPI_DRELU_F32 = 8, 9
 EPI_BIAS_GELU_GRAD_BF16, EPI_MUL_BF16, EPI_RAW_SLABS_F32 = 10, 11, 12
 EPI_BIAS_GELU_GRADQ_BF16, EPI_MULQ_BF16 = 13, 14      # GELU' as one-byte codes (ABI 12)
 TG_RAW, TG_BIAS, TG_BIAS_RELU, TG_DRELU = 0, 1, 2, 3
+TEMPORAL_MAX_S = 96                                    # SAIS_TEMPORAL_MAX_S_FWD / _BWD: the resident attention kernels
+TEMPORAL_LONG_MAX_S = 2001                             # SAIS_TEMPORAL_LONG_MAX_S: the streaming ones
 
 # name -> argtypes; every symbol include/sais_hip.h declares (checked by tests/test_abi.py)
 SIGNATURES = {
@@ -242,6 +244,11 @@ SIGNATURES = {
     "sais_temporal_attn_fwd": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, ctypes.c_uint, c_void_p],
     "sais_temporal_attn_bwd": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_long, c_void_p, c_float, c_void_p,
                                ctypes.c_uint, c_void_p],
+    # the same attention with keys and values streamed through LDS, S <= TEMPORAL_LONG_MAX_S (csrc/tattn_long.hip)
+    "sais_temporal_attn_long_bwd_workspace_bytes": [c_int, c_int],
+    "sais_temporal_attn_fwd_long": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, ctypes.c_uint, c_void_p],
+    "sais_temporal_attn_bwd_long": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_long, c_void_p, c_float, c_void_p,
+                                    ctypes.c_uint, c_void_p, ctypes.c_size_t, c_void_p],
     "sais_rng_advance": [c_void_p, c_void_p],
     "sais_droppath_scales": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, ctypes.c_uint, c_void_p],
     "sais_cast_bf16_rows": [c_void_p, c_void_p, c_void_p, c_long, c_int, c_void_p],
@@ -335,6 +342,7 @@ def load():
         fn.restype = c_int
     lib.sais_preprocess_plan_destroy.restype = None
     lib.sais_workspace_bytes.restype = ctypes.c_size_t
+    lib.sais_temporal_attn_long_bwd_workspace_bytes.restype = ctypes.c_size_t
     lib.sais_jpeg_workspace_bytes.restype = ctypes.c_size_t
     lib.sais_jpeg_mixed_workspace_bytes.restype = ctypes.c_size_t
     lib.sais_jpeg_encode_bound.restype = ctypes.c_size_t

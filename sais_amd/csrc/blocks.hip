@@ -42,7 +42,7 @@ extern "C" size_t sais_workspace_bytes(int op, int frames, int ntok) {
         case SAIS_OP_VIT_BLOCK_FWD: return ws_up(M * HID * 2);                    // GELU(u) when the caller does not keep it (inference)
         case SAIS_OP_VIT_BLOCK_BWD: return block_bwd_layout(M).total;
         case SAIS_OP_TEMPORAL_LAYER_FWD: return temporal_fwd_layout(M).total;
-        case SAIS_OP_TEMPORAL_LAYER_BWD: return temporal_bwd_layout(M).total;
+        case SAIS_OP_TEMPORAL_LAYER_BWD: return temporal_bwd_layout(M).total + temporal_long_attn_bytes(frames, ntok);
         default: return 0;
     }
 }
@@ -237,7 +237,11 @@ extern "C" int sais_temporal_layer_fwd(const SaisTemporalLayerParams* w, const S
     const unsigned long long* rng = p > 0.f ? a->rng_state : nullptr;
     // self-attention: in_proj -> per (sequence, head) softmax(q k^T / sqrt(96)) v with key-padding mask -> out_proj
     TRY(tg(a->z, w->in_proj_w, M, QKV, D, SAIS_TG_BIAS, 1, w->in_proj_b, nullptr, a->qkv, 0.f, nullptr, 0, stream));
-    TRY(sais_temporal_attn_fwd(a->qkv, a->key_pad, a->B, a->S, a->ctx, a->attn_avg, p, rng, a->site0, stream));
+    // S <= 96: q, k, v resident in LDS (tattn.hip); longer sequences stream their keys (tattn_long.hip)
+    if (a->S <= SAIS_TEMPORAL_MAX_S_FWD)
+        TRY(sais_temporal_attn_fwd(a->qkv, a->key_pad, a->B, a->S, a->ctx, a->attn_avg, p, rng, a->site0, stream));
+    else
+        TRY(sais_temporal_attn_fwd_long(a->qkv, a->key_pad, a->B, a->S, a->ctx, a->attn_avg, p, rng, a->site0, stream));
     TRY(tg(a->ctx, w->out_proj_w, M, D, D, SAIS_TG_RAW, l.ns_out, nullptr, nullptr, slabs, 0.f, nullptr, 0, stream));
     TRY(sais_temporal_ln_fwd(slabs, l.ns_out, (long)M * D, w->out_proj_b, a->z, M, p, rng, a->site0 + 1, a->y1, w->norm1_g, w->norm1_b,
                              1e-5f, a->z1, a->mean1, a->rstd1, stream));
@@ -262,7 +266,8 @@ extern "C" int sais_temporal_layer_bwd(const SaisTemporalLayerParams* w, const S
     if (a->p_drop < 0.f || a->p_drop >= 1.f || (a->p_drop > 0.f && !a->rng_state)) return SAIS_ERR_ARG;
     const int M = a->B * a->S;
     const TemporalBwdLayout l = temporal_bwd_layout((size_t)a->B * a->S);
-    if (!workspace || ws_bytes < l.total || ((uintptr_t)workspace & 15)) return SAIS_ERR_ARG;
+    const size_t long_bytes = temporal_long_attn_bytes(a->B, a->S);
+    if (!workspace || ws_bytes < l.total + long_bytes || ((uintptr_t)workspace & 15)) return SAIS_ERR_ARG;
     const float p = a->p_drop;
     const unsigned long long* rng = p > 0.f ? a->rng_state : nullptr;
     char* const ws = (char*)workspace;
@@ -280,7 +285,11 @@ extern "C" int sais_temporal_layer_bwd(const SaisTemporalLayerParams* w, const S
                              p > 0.f ? dt1 : nullptr, p, rng, a->site0 + 1, w->d_norm1_g, w->d_norm1_b, stream));
     // attention: d ctx = g1 . Wo (raw slabs, summed on load by the attention backward)
     TRY(tg(g1, w->out_proj_wt, M, D, D, SAIS_TG_RAW, l.nso, nullptr, nullptr, slabo, 0.f, nullptr, 0, stream));
-    TRY(sais_temporal_attn_bwd(a->qkv, a->key_pad, a->B, a->S, slabo, l.nso, (long)M * D, dqkv, p, rng, a->site0, stream));
+    if (a->S <= SAIS_TEMPORAL_MAX_S_BWD)
+        TRY(sais_temporal_attn_bwd(a->qkv, a->key_pad, a->B, a->S, slabo, l.nso, (long)M * D, dqkv, p, rng, a->site0, stream));
+    else
+        TRY(sais_temporal_attn_bwd_long(a->qkv, a->key_pad, a->B, a->S, slabo, l.nso, (long)M * D, dqkv, p, rng, a->site0,
+                                        ws + l.total, long_bytes, stream));
     // the four weight / bias gradients of the layer in one launch (one M-split: owner-computes, no atomics)
     SaisTnItem items[4] = {
         {g2, D, a->h, FF, D, FF, w->d_linear2_w, FF, w->d_linear2_b},

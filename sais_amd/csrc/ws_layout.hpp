@@ -36,3 +36,7 @@ static inline TemporalBwdLayout temporal_bwd_layout(size_t M) {
     l.slabo = l.slab1 + (size_t)l.ns1 * M * D * 4; l.total = o;
     return l;
 }
+// S > SAIS_TEMPORAL_MAX_S_BWD: the workspace of the streaming attention backward sits behind that layout (0 bytes up to it)
+static inline size_t temporal_long_attn_bytes(int B, int S) {
+    return S > SAIS_TEMPORAL_MAX_S_BWD ? ws_up(sais_temporal_attn_long_bwd_workspace_bytes(B, S)) : 0;
+}

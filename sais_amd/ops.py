@@ -740,6 +740,38 @@ def temporal_attn_bwd(qkv, key_pad_u8, B, S, dctx, dqkv, p_drop=0.0, rng=None, s
            _p(rng), site, _stream())
 
 
+# ---- the same attention with keys and values streamed through LDS: S <= L.TEMPORAL_LONG_MAX_S (csrc/tattn_long.hip)
+def temporal_attn_long_bwd_workspace_bytes(B, S):
+    return int(L.load().sais_temporal_attn_long_bwd_workspace_bytes(B, S))
+
+
+def temporal_attn_fwd_long(qkv, key_pad_u8, B, S, ctx, attn_avg=None, p_drop=0.0, rng=None, site=0):
+    """attn_avg needs no pre-zeroing; ctx and attn_avg are bit-reproducible."""
+    L.call("sais_temporal_attn_fwd_long", _p(qkv), _p(key_pad_u8), B, S, _p(ctx), _p(attn_avg), float(p_drop), _p(rng), site,
+           _stream())
+
+
+def temporal_attn_bwd_long(qkv, key_pad_u8, B, S, dctx, dqkv, p_drop=0.0, rng=None, site=0, ws=None):
+    """dctx as temporal_attn_bwd takes it; ws: uint8 scratch of temporal_attn_long_bwd_workspace_bytes(B, S) (allocated here
+    when None)."""
+    nslab, stride = (dctx.shape[0], dctx.stride(0)) if dctx.dim() == 3 else (1, 0)
+    if ws is None:
+        ws = torch.empty(temporal_attn_long_bwd_workspace_bytes(B, S), dtype=torch.uint8, device=qkv.device)
+    L.call("sais_temporal_attn_bwd_long", _p(qkv), _p(key_pad_u8), B, S, _p(dctx), nslab, stride, _p(dqkv), float(p_drop),
+           _p(rng), site, _p(ws), ws.numel(), _stream())
+
+
+def temporal_attn_fwd_any(qkv, key_pad_u8, B, S, ctx, attn_avg=None, p_drop=0.0, rng=None, site=0):
+    """The form sais_temporal_layer_fwd picks: resident in LDS up to L.TEMPORAL_MAX_S tokens, streaming past it."""
+    fn = temporal_attn_fwd if S <= L.TEMPORAL_MAX_S else temporal_attn_fwd_long
+    fn(qkv, key_pad_u8, B, S, ctx, attn_avg, p_drop, rng, site)
+
+
+def temporal_attn_bwd_any(qkv, key_pad_u8, B, S, dctx, dqkv, p_drop=0.0, rng=None, site=0):
+    fn = temporal_attn_bwd if S <= L.TEMPORAL_MAX_S else temporal_attn_bwd_long
+    fn(qkv, key_pad_u8, B, S, dctx, dqkv, p_drop, rng, site)
+
+
 # ---- train-mode dropout: rng = int64 device tensor {seed, offset} (include/sais_hip.h)
 def rng_state(seed, device):
     return torch.tensor([int(seed), 0], dtype=torch.int64, device=device)

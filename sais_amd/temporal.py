@@ -402,7 +402,7 @@ class fullModel(nn.Module):
         ops.tgemm(t["z"], fl.w32(p + "self_attn.in_proj_weight"), L.TG_BIAS, t["qkv"], bias=fl.w32(p + "self_attn.in_proj_bias"))
         # train mode: dropout sites 0-3 of this layer (attention weights, dropout1, dropout, dropout2), fused into the consumers
         pd, rng = drop if drop is not None else (0.0, None)
-        ops.temporal_attn_fwd(t["qkv"], pad, B, S, t["ctx"], amap, p_drop=pd, rng=rng, site=site)
+        ops.temporal_attn_fwd_any(t["qkv"], pad, B, S, t["ctx"], amap, p_drop=pd, rng=rng, site=site)     # S > 96: the streaming form
         # src = norm1(src + dropout1(out_proj(ctx)))
         ops.temporal_ln_fwd(self._raw(t["ctx"], fl.w32(p + "self_attn.out_proj.weight")), fl.w32(p + "self_attn.out_proj.bias"),
                             t["z"], fl.w32(p + "norm1.weight"), fl.w32(p + "norm1.bias"), 1e-5, t["z1"], y=t["y1"], mean=t["m1"],
@@ -518,8 +518,8 @@ class fullModel(nn.Module):
                                 fl.w32(p + "norm1.weight"), dy1, dx_drop=None if drop is None else dt1,
                                 drop=self._drop3(drop, site + 1), dgamma=fl.g(p + "norm1.weight"), dbeta=fl.g(p + "norm1.bias"))
             dqkv = e32(M, 3 * D)
-            ops.temporal_attn_bwd(a["qkv"], s["pad"], B, S, self._raw(dt1, fl.wt16[p + "self_attn.out_proj.weight"]), dqkv,
-                                  p_drop=pd, rng=rng, site=site)
+            ops.temporal_attn_bwd_any(a["qkv"], s["pad"], B, S, self._raw(dt1, fl.wt16[p + "self_attn.out_proj.weight"]), dqkv,
+                                      p_drop=pd, rng=rng, site=site)
             # the four weight / bias gradients of the layer in one launch (M is a few hundred rows: launch-bound); one M-split:
             # every workgroup owns its output tile and accumulates without atomics
             ops.gemm_tn_grouped([
