@@ -371,7 +371,6 @@ __global__ __launch_bounds__(G::BWD_THREADS) void attn_bwd_kernel(const bf16* qk
 //                           32-key steps.
 // S, dP and the exponential are computed twice (7 product groups instead of 5, 2 x the VALU work) — on pipes that idled — and
 // the only barriers are the two around the staging of a problem.  13 waves (832 threads) for 197 tokens, one workgroup per CU.
-template <class G> struct NbTag {};
 template <class G> constexpr int bwd_nb_lds() { return 4 * G::MAT_BYTES + 2 * G::TILE_ROWS * 4; }
 
 template <class G>
@@ -533,23 +532,9 @@ __global__ __launch_bounds__(G::NKT * 64) void attn_bwd_nb_kernel(const bf16* qk
 
 template <class G> constexpr int fwd_lds() { return 2 * G::MAT_BYTES; }
 
-// raise the dynamic-LDS limit of a kernel once per process and device (not per call: keeps the launch
-// path free of runtime-API calls so it can be captured into a hipGraph); the limit only ever grows.
-template <class Tag, typename K>          // Tag: one `granted` table per kernel INSTANCE (K alone is only the signature)
-int set_lds(K kernel, int bytes) {
-    static thread_local int granted[16] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return SAIS_ERR_LAUNCH;
-    if (bytes <= granted[dev]) return SAIS_OK;
-    if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
-        return SAIS_ERR_LAUNCH;
-    granted[dev] = bytes;
-    return SAIS_OK;
-}
-
 template <class G>
 int launch_fwd(const void* qkv, long ldqkv, int frames, void* out, long ldo, float* lse, float* probs, void* stream) {
-    if (set_lds<G>(attn_fwd_kernel<G>, fwd_lds<G>())) return SAIS_ERR_LAUNCH;
+    if (sais_grow_dyn_lds<attn_fwd_kernel<G>>(fwd_lds<G>())) return SAIS_ERR_LAUNCH;
     hipLaunchKernelGGL(attn_fwd_kernel<G>, dim3(NH, frames), dim3(256), fwd_lds<G>(), (hipStream_t)stream,
                        (const bf16*)qkv, ldqkv, (bf16*)out, ldo, lse, probs, 0.125f);
     return sais_check_launch();
@@ -564,7 +549,7 @@ int launch_bwd(const void* qkv, long ldqkv, const void* dout, long lddo, const v
     static const bool nb = sais_env_int("SAIS_ATTN_BWD_NB", SAIS_ATTN_BWD_NB_DEFAULT) != 0;
     if constexpr (G::NKT > 4) {
         if (nb) {
-            if (set_lds<NbTag<G>>(attn_bwd_nb_kernel<G>, bwd_nb_lds<G>())) return SAIS_ERR_LAUNCH;
+            if (sais_grow_dyn_lds<attn_bwd_nb_kernel<G>>(bwd_nb_lds<G>())) return SAIS_ERR_LAUNCH;
             hipLaunchKernelGGL(attn_bwd_nb_kernel<G>, dim3(nprob < 256 ? nprob : 256), dim3(G::NKT * 64), bwd_nb_lds<G>(),
                                (hipStream_t)stream, (const bf16*)qkv, ldqkv, (const bf16*)dout, lddo, (const bf16*)out, ldout, lse,
                                nprob, (bf16*)dqkv, lddqkv, 0.125f);
@@ -572,7 +557,7 @@ int launch_bwd(const void* qkv, long ldqkv, const void* dout, long lddo, const v
         }
     }
 #endif
-    if (set_lds<G>(attn_bwd_kernel<G>, bwd_lds<G>())) return SAIS_ERR_LAUNCH;
+    if (sais_grow_dyn_lds<attn_bwd_kernel<G>>(bwd_lds<G>())) return SAIS_ERR_LAUNCH;
     // short sequences leave most of the LDS free: several workgroups per CU
     int per_cu = 160 * 1024 / bwd_lds<G>();                       // resident workgroups per CU (LDS-limited)
     per_cu = G::BWD_THREADS == 1024 ? 1 : (per_cu > 4 ? 4 : per_cu);

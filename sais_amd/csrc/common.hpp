@@ -239,6 +239,20 @@ static inline bool sais_dyn_lds_once(int bytes) {
     if (!set) set = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
     return set;
 }
+// The same limit for a kernel whose need depends on the call: raised per device when a call needs more than was granted, never
+// lowered, and no runtime call once granted (the launch path stays capturable into a hipGraph).  Keyed on the kernel itself,
+// so two kernels of one signature never share a grant.  Returns SAIS_OK or SAIS_ERR_LAUNCH
+template <auto KERNEL>
+static inline int sais_grow_dyn_lds(int bytes) {
+    static thread_local int granted[16] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return SAIS_ERR_LAUNCH;
+    if (bytes <= granted[dev]) return SAIS_OK;
+    if (hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
+        return SAIS_ERR_LAUNCH;
+    granted[dev] = bytes;
+    return SAIS_OK;
+}
 
 // -DSAIS_EXPERIMENTAL=1 (tools/build_variant.sh exp -DSAIS_EXPERIMENTAL=1) adds the rejected kernel forms kept as experiment records
 #ifndef SAIS_EXPERIMENTAL

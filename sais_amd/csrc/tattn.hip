@@ -15,8 +15,9 @@
 // 16-key tile: softmax is an in-lane loop plus two shuffles, and P^T is already the B operand of ctx^T = V^T P^T (slot g of
 // step r <-> key 4 g + r) with no lane movement.  The backward needs P and dS with the KEY on the lane as well (dV, dK sum
 // over queries): the waves re-own key tiles after a barrier and rebuild both from the per-query statistics left in LDS.
+// The arithmetic this file has in common with tattn_long.hip (score scale, dropout rule, masked score tile, 4-key accumulate,
+// dK / dV step) is written once, in tattn_frag.hpp; here are the staging and the softmax of the resident form.
 #include "tattn_frag.hpp"
-#include "philox.hpp"
 #include "../../include/sais_hip.h"
 
 namespace {
@@ -57,8 +58,7 @@ DEVINL void stage_pad(const unsigned char* pad, int S, int Spad, unsigned char* 
 
 constexpr int MAXT = 6;                                  // 16-token tiles: S <= 96
 
-// Train mode (p > 0): the attention weights are dropped AFTER the softmax and BEFORE P v, and the returned map is the
-// dropped one (torch-1.8 F.multi_head_attention_forward).  Mask element index: ((b * 4 + h) * S + i) * S + j.
+// Train mode (p > 0): the dropped weights go into P v and into the returned map (Drop, tattn_frag.hpp).
 __global__ __launch_bounds__(256) void tattn_fwd_kernel(const float* qkv, const unsigned char* key_pad, int S, float* ctx,
                                                        float* attn_avg, float p_drop, const unsigned long long* rng,
                                                        unsigned sid) {
@@ -73,14 +73,11 @@ __global__ __launch_bounds__(256) void tattn_fwd_kernel(const float* qkv, const 
     stage_pad(key_pad + (size_t)b * S, S, Spad, sP, tid);
     stage_qkv(qkv, b, h, S, Spad, sQ, sK, sV, tid);
     __syncthreads();
-    const bool dropping = p_drop > 0.f;
-    const unsigned thr = drop_threshold(p_drop);
-    const float inv_keep = dropping ? 1.0f / (1.0f - p_drop) : 1.0f;
-    const unsigned long long base = ((unsigned long long)b * TH + h) * S * S;
+    const Drop drop(p_drop, rng, sid, b, h, S);
     for (int qt = wid; qt < nt; qt += 4) {
         const int q = 16 * qt + li;                      // this lane's query (column of S^T)
         float qf[24];
-        load24(sQ + q * TLD, g, qf, 0.10206207261596577f /* 96^-0.5 */);
+        load24(sQ + q * TLD, g, qf, QSCALE);
         f32x4 p[MAXT];
         float m = -INFINITY;
 #pragma unroll
@@ -98,11 +95,7 @@ __global__ __launch_bounds__(256) void tattn_fwd_kernel(const float* qkv, const 
 #pragma unroll
         for (int kt = 0; kt < MAXT; ++kt) {
             if (kt >= nt) break;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (sP[16 * kt + 4 * g + r]) p[kt][r] = -INFINITY;
-                m = fmaxf(m, p[kt][r]);
-            }
+            mask_tile(sP, 16 * kt, g, p[kt], m);
         }
         m = group_max(m);
         float sum = 0.f;
@@ -120,31 +113,20 @@ __global__ __launch_bounds__(256) void tattn_fwd_kernel(const float* qkv, const 
             for (int r = 0; r < 4; ++r) {
                 const int key = 16 * kt + 4 * g + r;
                 float v = p[kt][r] * inv;
-                if (dropping && q < S && key < S)
-                    v = philox_keep(rng, sid, base + (unsigned long long)q * S + key, thr) ? v * inv_keep : 0.f;
+                if (drop.on && q < S && key < S) v *= drop.keep(q, key);
                 p[kt][r] = v;
                 if (attn_avg && q < S && key < S) atomicAdd(attn_avg + ((size_t)b * S + q) * S + key, v * (1.0f / TH));
             }
         }
         // ctx^T[d][query] = sum_key v[key][d] P^T[key][query]: six independent accumulator chains (one per 16 features)
-        f32x4 acc[THD / 16];
-#pragma unroll
-        for (int dt = 0; dt < THD / 16; ++dt) acc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        Acc6 acc;
+        zero6(acc);
 #pragma unroll
         for (int kt = 0; kt < MAXT; ++kt) {
             if (kt >= nt) break;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float* vrow = sV + (16 * kt + 4 * g + r) * TLD + li;
-#pragma unroll
-                for (int dt = 0; dt < THD / 16; ++dt) acc[dt] = mfma4(vrow[16 * dt], p[kt][r], acc[dt]);
-            }
+            accumulate4(sV, 16 * kt, p[kt], g, li, acc);
         }
-        if (q < S) {
-#pragma unroll
-            for (int dt = 0; dt < THD / 16; ++dt)
-                *(f32x4*)(ctx + ((size_t)b * S + q) * D + h * THD + 16 * dt + 4 * g) = acc[dt];
-        }
+        if (q < S) store6(ctx + ((size_t)b * S + q) * D + h * THD, g, acc);
     }
 }
 
@@ -165,7 +147,6 @@ __global__ __launch_bounds__(256) void tattn_bwd_kernel(const float* qkv, const 
     unsigned char* sP = (unsigned char*)(sDot + Spad);
     const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int g = lane >> 4, li = lane & 15;
-    const float scale = 0.10206207261596577f;
     stage_pad(key_pad + (size_t)b * S, S, Spad, sP, tid);
     {   // dctx = sum of the out_proj dX slabs: the loads of SU passes x one slab in flight together
         const int total = Spad * (THD / 4);
@@ -194,35 +175,20 @@ __global__ __launch_bounds__(256) void tattn_bwd_kernel(const float* qkv, const 
     }
     stage_qkv(qkv, b, h, S, Spad, sQ, sK, sV, tid);
     __syncthreads();
-    const bool dropping = p_drop > 0.f;
-    const unsigned thr = drop_threshold(p_drop);
-    const float inv_keep = dropping ? 1.0f / (1.0f - p_drop) : 1.0f;
-    const unsigned long long base = ((unsigned long long)b * TH + h) * S * S;
-    auto keep_of = [&](int q, int key) {
-        return (!dropping || philox_keep(rng, sid, base + (unsigned long long)q * S + key, thr)) ? inv_keep : 0.f;
-    };
+    const Drop drop(p_drop, rng, sid, b, h, S);
 
     // ---- phase 1: a wave owns 16 queries (on the lane), all keys: statistics, dS^T, dq
     for (int qt = wid; qt < nt; qt += 4) {
         const int q = 16 * qt + li;
         float qf[24], gf[24];
-        load24(sQ + q * TLD, g, qf, scale);
+        load24(sQ + q * TLD, g, qf, QSCALE);
         load24(sG + q * TLD, g, gf);
         f32x4 p[MAXT], dp[MAXT];
         float m = -INFINITY;
 #pragma unroll
         for (int kt = 0; kt < MAXT; ++kt) {
             if (kt >= nt) break;
-            float kf[24], vf[24];
-            load24(sK + (16 * kt + li) * TLD, g, kf);
-            load24(sV + (16 * kt + li) * TLD, g, vf);
-            dot_tile2(kf, qf, vf, gf, p[kt], dp[kt]);    // scores^T and dP'[query][key] = dctx_q . v_key (key 4 g + r on the registers)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int key = 16 * kt + 4 * g + r;
-                if (sP[key]) p[kt][r] = -INFINITY;
-                m = fmaxf(m, p[kt][r]);
-            }
+            score_dp_tile(sK, sV, sP, 16 * kt, qf, gf, g, li, p[kt], dp[kt], m);
         }
         m = group_max(m);
         float sum = 0.f;
@@ -241,7 +207,7 @@ __global__ __launch_bounds__(256) void tattn_bwd_kernel(const float* qkv, const 
             for (int r = 0; r < 4; ++r) {
                 const int key = 16 * kt + 4 * g + r;
                 const float pv = p[kt][r] * inv;
-                const float kp = (q < S && key < S) ? keep_of(q, key) : 0.f;
+                const float kp = (q < S && key < S) ? drop.keep(q, key) : 0.f;
                 p[kt][r] = pv;
                 dp[kt][r] *= kp;                         // dP = dP' m / (1 - p)
                 dot += pv * dp[kt][r];
@@ -253,27 +219,17 @@ __global__ __launch_bounds__(256) void tattn_bwd_kernel(const float* qkv, const 
         for (int kt = 0; kt < MAXT; ++kt) {
             if (kt >= nt) break;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) p[kt][r] = p[kt][r] * (dp[kt][r] - dot) * scale;      // dS^T[key][query]
+            for (int r = 0; r < 4; ++r) p[kt][r] = p[kt][r] * (dp[kt][r] - dot) * QSCALE;     // dS^T[key][query]
         }
         // dq^T[d][query] = sum_key k[key][d] dS^T[key][query]
-        f32x4 acc[THD / 16];
-#pragma unroll
-        for (int dt = 0; dt < THD / 16; ++dt) acc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        Acc6 acc;
+        zero6(acc);
 #pragma unroll
         for (int kt = 0; kt < MAXT; ++kt) {
             if (kt >= nt) break;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float* krow = sK + (16 * kt + 4 * g + r) * TLD + li;
-#pragma unroll
-                for (int dt = 0; dt < THD / 16; ++dt) acc[dt] = mfma4(krow[16 * dt], p[kt][r], acc[dt]);
-            }
+            accumulate4(sK, 16 * kt, p[kt], g, li, acc);
         }
-        if (q < S) {
-#pragma unroll
-            for (int dt = 0; dt < THD / 16; ++dt)
-                *(f32x4*)(dqkv + ((size_t)b * S + q) * (3 * D) + h * THD + 16 * dt + 4 * g) = acc[dt];
-        }
+        if (q < S) store6(dqkv + ((size_t)b * S + q) * (3 * D) + h * THD, g, acc);
     }
     __syncthreads();
 
@@ -284,61 +240,17 @@ __global__ __launch_bounds__(256) void tattn_bwd_kernel(const float* qkv, const 
         float kf[24], vf[24];
         load24(sK + key * TLD, g, kf);
         load24(sV + key * TLD, g, vf);
-        f32x4 adv[THD / 16], adk[THD / 16];
-#pragma unroll
-        for (int dt = 0; dt < THD / 16; ++dt) { adv[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; adk[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-        for (int qt = 0; qt < nt; ++qt) {
-            float xf[24], yf[24];
-            load24(sQ + (16 * qt + li) * TLD, g, xf, scale);
-            load24(sG + (16 * qt + li) * TLD, g, yf);
-            f32x4 s, dpp;                                // register r: query 16 qt + 4 g + r, key on the lane
-            dot_tile2(xf, kf, yf, vf, s, dpp);           // scores and dP'[query][key]
-            const f32x4 m4 = *(const f32x4*)(sM + 16 * qt + 4 * g);
-            const f32x4 i4 = *(const f32x4*)(sI + 16 * qt + 4 * g);
-            const f32x4 d4 = *(const f32x4*)(sDot + 16 * qt + 4 * g);
-            f32x4 pp, ds;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int q = 16 * qt + 4 * g + r;
-                const bool ok = key_ok && q < S;
-                const float pv = ok ? __expf(s[r] - m4[r]) * i4[r] : 0.f;
-                const float kp = ok ? keep_of(q, key) : 0.f;
-                pp[r] = pv * kp;                                              // P'
-                ds[r] = ok ? pv * (dpp[r] * kp - d4[r]) * scale : 0.f;        // dS
-            }
-            // dV^T[d][key] += sum_q dctx[q][d] P'[q][key] ;  dK^T[d][key] += sum_q q[q][d] dS[q][key]   (slot g of step r <-> query 4 g + r)
-#pragma unroll
-            for (int dt = 0; dt < THD / 16; ++dt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int row = (16 * qt + 4 * g + r) * TLD + 16 * dt + li;
-                    adv[dt] = mfma4(sG[row], pp[r], adv[dt]);
-                    adk[dt] = mfma4(sQ[row], ds[r], adk[dt]);
-                }
-        }
+        Acc6 adv, adk;
+        zero6(adv);
+        zero6(adk);
+        for (int qt = 0; qt < nt; ++qt)
+            dkv_step(sQ, sG, sM, sI, sDot, 16 * qt, 16 * qt, S, key, key_ok, kf, vf, drop, g, li, adv, adk);
         if (key < S) {
-            float* o = dqkv + ((size_t)b * S + key) * (3 * D) + D + h * THD + 4 * g;
-#pragma unroll
-            for (int dt = 0; dt < THD / 16; ++dt) {
-                *(f32x4*)(o + 16 * dt) = adk[dt];
-                *(f32x4*)(o + D + 16 * dt) = adv[dt];
-            }
+            float* o = dqkv + ((size_t)b * S + key) * (3 * D) + D + h * THD;
+            store6(o, g, adk);
+            store6(o + D, g, adv);
         }
     }
-}
-
-// raise the dynamic-LDS limit of a kernel once per process and device (not per call: keeps the launch
-// path free of runtime-API calls so it can be captured into a hipGraph); the limit only ever grows.
-template <typename K>
-int set_lds(K kernel, int bytes) {
-    static thread_local int granted[16] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return SAIS_ERR_LAUNCH;
-    if (bytes <= granted[dev]) return SAIS_OK;
-    if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
-        return SAIS_ERR_LAUNCH;
-    granted[dev] = bytes;
-    return SAIS_OK;
 }
 
 // zero-fill as a KERNEL node: the head-averaged map is accumulated with atomics over the four heads.  (Round 6: as a
@@ -357,7 +269,7 @@ extern "C" int sais_temporal_attn_fwd(const float* qkv, const unsigned char* key
     if (p_drop < 0.f || p_drop >= 1.f || (p_drop > 0.f && !rng_state)) return SAIS_ERR_ARG;
     const int Spad = (S + 15) / 16 * 16;
     const int lds = 3 * Spad * TLD * 4 + Spad;
-    if (set_lds(tattn_fwd_kernel, lds)) return SAIS_ERR_LAUNCH;
+    if (sais_grow_dyn_lds<tattn_fwd_kernel>(lds)) return SAIS_ERR_LAUNCH;
     hipStream_t s = (hipStream_t)stream;
     if (attn_avg) {
         const long n = (long)B * S * S;
@@ -377,7 +289,7 @@ extern "C" int sais_temporal_attn_bwd(const float* qkv, const unsigned char* key
     if (p_drop < 0.f || p_drop >= 1.f || (p_drop > 0.f && !rng_state)) return SAIS_ERR_ARG;
     const int Spad = (S + 15) / 16 * 16;
     const int lds = (4 * Spad * TLD + 3 * Spad) * 4 + Spad;
-    if (set_lds(tattn_bwd_kernel, lds)) return SAIS_ERR_LAUNCH;
+    if (sais_grow_dyn_lds<tattn_bwd_kernel>(lds)) return SAIS_ERR_LAUNCH;
     hipLaunchKernelGGL(tattn_bwd_kernel, dim3(TH, B), dim3(256), lds, (hipStream_t)stream, qkv, key_pad, S, dctx, nslab,
                        slab_stride, dqkv, p_drop, rng_state, site);
     return sais_check_launch();

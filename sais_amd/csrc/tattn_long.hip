@@ -10,8 +10,9 @@
 // over all query tiles, P recomputed from the statistics of the first launch.  ctx, dqkv AND the map are bit-reproducible:
 // the map's head sum has a fixed order (one workgroup loops over the four heads of its query tile and owns its map rows).
 //
-// Arithmetic: exact fp32 on v_mfma_f32_16x16x4_f32 (tattn_frag.hpp), scores transposed (key on the accumulator rows, query
-// on the lane) as in tattn.hip.  Online form, per 64-key tile: m' = max(m, tile max), alpha = exp(m - m'), l = l alpha +
+// Arithmetic: exact fp32 on v_mfma_f32_16x16x4_f32, scores transposed (key on the accumulator rows, query on the lane) as in
+// tattn.hip; what the two files compute alike (score scale, dropout rule, masked score tile, 4-key accumulate, dK / dV step)
+// is written once, in tattn_frag.hpp.  Online form, per 64-key tile: m' = max(m, tile max), alpha = exp(m - m'), l = l alpha +
 // sum exp(s - m'), acc = acc alpha + (exp(s - m') keep) v; ctx = acc / ((1 - p) l).  Each lane keeps the partial l of its own
 // 4 keys per 16; the four lane groups are added at the end (group_sum).  Map form: every wave runs that recurrence over its quarter
 // of each key tile, then m = max_w m_w, l = sum_w l_w exp(m_w - m) in wave order; P = exp(s - m) (1 / l), P' = P keep /
@@ -22,12 +23,10 @@
 // (b, h, query) the row max, 1 / row sum and rowsum(P dP) = three f32 [B, 4, S].  The entry point has no ctx argument, so
 // rowsum(P dP) = sum_j P_j keep_j / (1 - p) (dctx . v_j) is accumulated online in the statistics pass next to l.
 #include "tattn_frag.hpp"
-#include "philox.hpp"
 #include "../../include/sais_hip.h"
 
 namespace {
 constexpr int LT = 64;                                   // rows of a staging tile = queries (keys) a workgroup owns
-constexpr float QSCALE = 0.10206207261596577f;           // 96^-0.5
 
 // rows row0 .. row0 + 63 of the 96-float slice at `src` (row stride ld floats, S rows) -> dst [64][TLD]; rows >= S zero.
 // Addresses are clamped, the six loads of a lane are in flight before the first LDS write (stage_qkv of tattn.hip).
@@ -49,19 +48,10 @@ DEVINL void stage_flags(const unsigned char* pad, int row0, int S, unsigned char
     if (tid < LT) sP[tid] = row0 + tid >= S ? (unsigned char)1 : pad[row0 + tid];
 }
 
-struct Drop {
-    const unsigned long long* rng; unsigned sid, thr; unsigned long long base; int S; bool on; float inv_keep;
-    DEVINL Drop(float p, const unsigned long long* r, unsigned s, int b, int h, int S_)
-        : rng(r), sid(s), thr(drop_threshold(p)), base(((unsigned long long)b * TH + h) * S_ * S_), S(S_), on(p > 0.f),
-          inv_keep(p > 0.f ? 1.0f / (1.0f - p) : 1.0f) {}
-    // 1 / (1 - p) where (query, key) is kept, 0 where dropped
-    DEVINL float keep(int q, int key) const {
-        return (!on || philox_keep(rng, sid, base + (unsigned long long)q * S + key, thr)) ? inv_keep : 0.f;
-    }
-};
-
-// scaled scores of the staged 64-key tile against the lane's query (s[j][r]: key 16 j + 4 g + r), -inf on flagged keys
-DEVINL void tile_scores(const float* sK, const unsigned char* sP, const float (&qf)[24], int g, int li, f32x4 (&s)[4]) {
+// scaled scores of the staged 64-key tile against the lane's query (s[j][r]: key 16 j + 4 g + r), -inf on flagged keys; returns
+// the tile's max over the query's 64 keys
+DEVINL float tile_scores(const float* sK, const unsigned char* sP, const float (&qf)[24], int g, int li, f32x4 (&s)[4]) {
+    float m = -INFINITY;
 #pragma unroll
     for (int j = 0; j < 4; j += 2) {
         float kf[24], kg[24];
@@ -70,43 +60,21 @@ DEVINL void tile_scores(const float* sK, const unsigned char* sP, const float (&
         dot_tile2(kf, qf, kg, qf, s[j], s[j + 1]);
     }
 #pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            if (sP[16 * j + 4 * g + r]) s[j][r] = -INFINITY;
+    for (int j = 0; j < 4; ++j) mask_tile(sP, 16 * j, g, s[j], m);
+    return group_max(m);
 }
 // the same with dP'[query][key] = dctx_q . v_key next to it
-DEVINL void tile_scores_dp(const float* sK, const float* sV, const unsigned char* sP, const float (&qf)[24], const float (&gf)[24],
-                           int g, int li, f32x4 (&s)[4], f32x4 (&dp)[4]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        float kf[24], vf[24];
-        load24(sK + (16 * j + li) * TLD, g, kf);
-        load24(sV + (16 * j + li) * TLD, g, vf);
-        dot_tile2(kf, qf, vf, gf, s[j], dp[j]);
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            if (sP[16 * j + 4 * g + r]) s[j][r] = -INFINITY;
-    }
-}
-DEVINL float tile_max(const f32x4 (&s)[4]) {
+DEVINL float tile_scores_dp(const float* sK, const float* sV, const unsigned char* sP, const float (&qf)[24], const float (&gf)[24],
+                            int g, int li, f32x4 (&s)[4], f32x4 (&dp)[4]) {
     float m = -INFINITY;
 #pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) m = fmaxf(m, s[j][r]);
+    for (int j = 0; j < 4; ++j) score_dp_tile(sK, sV, sP, 16 * j, qf, gf, g, li, s[j], dp[j], m);
     return group_max(m);
 }
 // acc^T[d][query] += sum_key x[key][d] w^T[key][query] over the staged tile (x = sV: ctx; x = sK: dq)
-DEVINL void tile_accumulate(const float* sX, const f32x4 (&w)[4], int g, int li, f32x4 (&acc)[THD / 16]) {
+DEVINL void tile_accumulate(const float* sX, const f32x4 (&w)[4], int g, int li, Acc6& acc) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float* row = sX + (16 * j + 4 * g + r) * TLD + li;
-#pragma unroll
-            for (int dt = 0; dt < THD / 16; ++dt) acc[dt] = mfma4(row[16 * dt], w[j][r], acc[dt]);
-        }
+    for (int j = 0; j < 4; ++j) accumulate4(sX, 16 * j, w[j], g, li, acc);
 }
 
 // grid (query tiles, 4 heads, B): one pass with online rescaling, no map
@@ -123,9 +91,8 @@ __global__ __launch_bounds__(256) void tattn_long_fwd_kernel(const float* qkv, c
     float qf[24];
     load24(seq + (size_t)min(q, S - 1) * (3 * D) + h * THD, g, qf, QSCALE);
     float m = -INFINITY, l = 0.f;
-    f32x4 acc[THD / 16];
-#pragma unroll
-    for (int dt = 0; dt < THD / 16; ++dt) acc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    Acc6 acc;
+    zero6(acc);
     for (int kt = 0; kt < nkt; ++kt) {
         __syncthreads();
         stage_tile(seq + D + h * THD, 3 * D, LT * kt, S, sK, tid);
@@ -133,8 +100,7 @@ __global__ __launch_bounds__(256) void tattn_long_fwd_kernel(const float* qkv, c
         stage_flags(pad, LT * kt, S, sP, tid);
         __syncthreads();
         f32x4 s[4];
-        tile_scores(sK, sP, qf, g, li, s);
-        const float mn = fmaxf(m, tile_max(s));          // move the running max, rescale what is accumulated
+        const float mn = fmaxf(m, tile_scores(sK, sP, qf, g, li, s));      // move the running max, rescale what is accumulated
         const float alpha = __expf(m - mn);
         m = mn;
         l *= alpha;
@@ -153,11 +119,9 @@ __global__ __launch_bounds__(256) void tattn_long_fwd_kernel(const float* qkv, c
         tile_accumulate(sV, s, g, li, acc);
     }
     const float fin = drop.inv_keep / group_sum(l);
-    if (q < S) {
 #pragma unroll
-        for (int dt = 0; dt < THD / 16; ++dt)
-            *(f32x4*)(ctx + ((size_t)b * S + q) * D + h * THD + 16 * dt + 4 * g) = acc[dt] * fin;
-    }
+    for (int dt = 0; dt < THD / 16; ++dt) acc[dt] *= fin;
+    if (q < S) store6(ctx + ((size_t)b * S + q) * D + h * THD, g, acc);
 }
 
 // The map form.  grid (16-query tiles, 1, B): the workgroup owns 16 queries and their rows of attn_avg and loops over the four
@@ -193,7 +157,7 @@ __global__ __launch_bounds__(256) void tattn_long_fwd_map_kernel(const float* qk
             float kf[24];
             load24(sK + (16 * wid + li) * TLD, g, kf);
             f32x4 s = dot_tile(kf, qf);                   // register r: key 16 wid + 4 g + r of the tile, query q
-            float mt = -INFINITY;
+            float mt = -INFINITY;                         // own copy of mask_tile (tattn_frag.hpp): keep the two in step
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 if (sP[16 * wid + 4 * g + r]) s[r] = -INFINITY;
@@ -215,9 +179,8 @@ __global__ __launch_bounds__(256) void tattn_long_fwd_map_kernel(const float* qk
         for (int w = 0; w < 4; ++w) L += sL[w][li] * __expf(sM[w][li] - M);          // a wave without a key: 0 exp(-inf) = 0
         const float inv = 1.0f / L;
         // ---- pass 2
-        f32x4 acc[THD / 16];
-#pragma unroll
-        for (int dt = 0; dt < THD / 16; ++dt) acc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        Acc6 acc;
+        zero6(acc);
         for (int kt = 0; kt < nkt; ++kt) {
             __syncthreads();
             stage_tile(seq + D + h * THD, 3 * D, LT * kt, S, sK, tid);
@@ -237,7 +200,7 @@ __global__ __launch_bounds__(256) void tattn_long_fwd_map_kernel(const float* qk
                     float* a = attn_avg + ((size_t)b * S + q) * S + key;
                     *a = h == 0 ? v * (1.0f / TH) : *a + v * (1.0f / TH);
                 }
-                const float* row = sV + (16 * wid + 4 * g + r) * TLD + li;
+                const float* row = sV + (16 * wid + 4 * g + r) * TLD + li;         // own copy of a step of accumulate4
 #pragma unroll
                 for (int dt = 0; dt < THD / 16; ++dt) acc[dt] = mfma4(row[16 * dt], v, acc[dt]);
             }
@@ -292,8 +255,7 @@ __global__ __launch_bounds__(256) void tattn_long_bwd_dq_kernel(const float* qkv
         stage_flags(pad, LT * kt, S, sP, tid);
         __syncthreads();
         f32x4 s[4], dp[4];
-        tile_scores_dp(sK, sV, sP, qf, gf, g, li, s, dp);
-        const float mn = fmaxf(m, tile_max(s));
+        const float mn = fmaxf(m, tile_scores_dp(sK, sV, sP, qf, gf, g, li, s, dp));
         const float alpha = __expf(m - mn);
         m = mn;
         l *= alpha;
@@ -315,9 +277,8 @@ __global__ __launch_bounds__(256) void tattn_long_bwd_dq_kernel(const float* qkv
         wsM[o] = m; wsI[o] = inv; wsDot[o] = dot;
     }
     // ---- pass 2: dS^T on the registers, dq^T[d][query] = sum_key k[key][d] dS^T[key][query]
-    f32x4 acc[THD / 16];
-#pragma unroll
-    for (int dt = 0; dt < THD / 16; ++dt) acc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    Acc6 acc;
+    zero6(acc);
     for (int kt = 0; kt < nkt; ++kt) {
         __syncthreads();
         stage_tile(seq + D + h * THD, 3 * D, LT * kt, S, sK, tid);
@@ -337,11 +298,7 @@ __global__ __launch_bounds__(256) void tattn_long_bwd_dq_kernel(const float* qkv
             }
         tile_accumulate(sK, s, g, li, acc);
     }
-    if (q < S) {
-#pragma unroll
-        for (int dt = 0; dt < THD / 16; ++dt)
-            *(f32x4*)(dqkv + ((size_t)b * S + q) * (3 * D) + h * THD + 16 * dt + 4 * g) = acc[dt];
-    }
+    if (q < S) store6(dqkv + ((size_t)b * S + q) * (3 * D) + h * THD, g, acc);
 }
 
 // grid (key tiles, 4 heads, B): a wave owns 16 keys (on the lane) and loops over the query tiles; P' and dS rebuilt from the
@@ -363,9 +320,9 @@ __global__ __launch_bounds__(256) void tattn_long_bwd_dkv_kernel(const float* qk
     float kf[24], vf[24];
     load24(seq + (size_t)kc * (3 * D) + D + h * THD, g, kf);
     load24(seq + (size_t)kc * (3 * D) + 2 * D + h * THD, g, vf);
-    f32x4 adv[THD / 16], adk[THD / 16];
-#pragma unroll
-    for (int dt = 0; dt < THD / 16; ++dt) { adv[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; adk[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    Acc6 adv, adk;
+    zero6(adv);
+    zero6(adk);
     for (int qt = 0; qt < nqt; ++qt) {
         __syncthreads();
         stage_tile(seq + h * THD, 3 * D, LT * qt, S, sQ, tid);
@@ -376,42 +333,13 @@ __global__ __launch_bounds__(256) void tattn_long_bwd_dkv_kernel(const float* qk
         }
         __syncthreads();
 #pragma unroll 1
-        for (int j = 0; j < 4; ++j) {
-            float xf[24], yf[24];
-            load24(sQ + (16 * j + li) * TLD, g, xf, QSCALE);
-            load24(sG + (16 * j + li) * TLD, g, yf);
-            f32x4 s, dpp;                                // register r: query 16 j + 4 g + r of the tile, key on the lane
-            dot_tile2(xf, kf, yf, vf, s, dpp);
-            const f32x4 m4 = *(const f32x4*)(sM + 16 * j + 4 * g);
-            const f32x4 i4 = *(const f32x4*)(sI + 16 * j + 4 * g);
-            const f32x4 d4 = *(const f32x4*)(sDot + 16 * j + 4 * g);
-            f32x4 pp, ds;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int q = LT * qt + 16 * j + 4 * g + r;
-                const bool ok = key_ok && q < S;
-                const float pv = ok ? __expf(s[r] - m4[r]) * i4[r] : 0.f;
-                const float kp = ok ? drop.keep(q, key) : 0.f;
-                pp[r] = pv * kp;
-                ds[r] = ok ? pv * (dpp[r] * kp - d4[r]) * QSCALE : 0.f;
-            }
-#pragma unroll
-            for (int dt = 0; dt < THD / 16; ++dt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int row = (16 * j + 4 * g + r) * TLD + 16 * dt + li;
-                    adv[dt] = mfma4(sG[row], pp[r], adv[dt]);
-                    adk[dt] = mfma4(sQ[row], ds[r], adk[dt]);
-                }
-        }
+        for (int j = 0; j < 4; ++j)
+            dkv_step(sQ, sG, sM, sI, sDot, 16 * j, LT * qt + 16 * j, S, key, key_ok, kf, vf, drop, g, li, adv, adk);
     }
     if (key < S) {
-        float* o = dqkv + ((size_t)b * S + key) * (3 * D) + D + h * THD + 4 * g;
-#pragma unroll
-        for (int dt = 0; dt < THD / 16; ++dt) {
-            *(f32x4*)(o + 16 * dt) = adk[dt];
-            *(f32x4*)(o + D + 16 * dt) = adv[dt];
-        }
+        float* o = dqkv + ((size_t)b * S + key) * (3 * D) + D + h * THD;
+        store6(o, g, adk);
+        store6(o + D, g, adv);
     }
 }
 

@@ -94,8 +94,12 @@ def test_mask_index_is_64_bit():
     assert 4 * S * S * 268 < 2 ** 32 <= 4 * S * S * 269
     assert LR.mask_index(268, 3, S - 1, S - 1, S, bits=32) != LR.mask_index(268, 3, S - 1, S - 1, S)
     assert LR.mask_index(1, 2, 3, 4, 97) == ((1 * 4 + 2) * 97 + 3) * 97 + 4
-    src = _src("sais_amd", "csrc", "tattn_long.hip")
+    src = _src("sais_amd", "csrc", "tattn_frag.hpp")
     assert "base(((unsigned long long)b * TH + h) * S_ * S_)" in src and "base + (unsigned long long)q * S + key" in src
+    # the one dropout rule serves the resident and the streaming kernels: neither file draws a mask of its own
+    assert src.count("philox_keep(") == 1
+    for name in ("tattn.hip", "tattn_long.hip"):
+        assert "philox_keep(" not in _src("sais_amd", "csrc", name), name
 
 
 def test_long_launcher_rules_match_the_sources():
