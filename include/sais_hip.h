@@ -456,7 +456,8 @@ int sais_touch(const void* p, long bytes, void* stream);
 
 /* ---------------------------------------------------------------- optimizer + weight shadows
  * optim.SGD(params, lr) — prepare_model.py:566-567, perform_training.py:155-158 (no momentum / wd).
- * param -= lr * grad_scale * grad; shadow_bf16 (optional) refreshed in the same pass.            */
+ * param -= lr * grad_scale * grad; shadow_bf16 (optional) refreshed in the same pass.
+ * param, grad 16-B aligned, shadow_bf16 8-B aligned: SAIS_ERR_ARG otherwise.                     */
 int sais_sgd_step(float* param, const float* grad, void* shadow_bf16, long n, float lr, float grad_scale, void* stream);
 int sais_cast_bf16(const float* src, void* dst_bf16, long n, void* stream);
 int sais_transpose_cast_bf16(const float* src, int rows, int cols, void* dst_bf16 /*[cols,rows]*/, void* stream);

@@ -232,7 +232,9 @@ __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const float* dout, cons
     load_row(dout + (size_t)r * dim, dim, lane, g);
     load_row(out + (size_t)r * dim, dim, lane, o);
     const float iv = inv[r];
-    const float d = iv * eps >= 1.0f ? 0.f : dot_rows(g, o);
+    // clamp row: the forward stored exactly 1.0f / eps (its own expression with fmaxf(., eps) = eps).  `iv * eps >= 1.0f` is false
+    // for about one eps in seven (1.3e-8, 2.7e-5), where fl(fl(1 / eps) eps) < 1, and such a row then kept the projection
+    const float d = iv >= 1.0f / eps ? 0.f : dot_rows(g, o);
 #pragma unroll
     for (int j = 0; j < ROWV; ++j) g[j] = (g[j] - o[j] * d) * iv;
     store_row(dz + (size_t)r * dim, dim, lane, g);

@@ -276,6 +276,7 @@ extern "C" int sais_sgd_step(float* param, const float* grad, void* shadow_bf16,
     SAIS_ENTER();
     if (!param || !grad || n <= 0) return SAIS_ERR_ARG;
     if (((uintptr_t)param | (uintptr_t)grad) & 15) return SAIS_ERR_ARG;
+    if ((uintptr_t)shadow_bf16 & 7) return SAIS_ERR_ARG;               // the bf16x4 shadow store
     hipLaunchKernelGGL(sgd_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, param, grad,
                        (bf16*)shadow_bf16, n, lr, grad_scale);
     return sais_check_launch();

@@ -130,6 +130,7 @@ def test_gelu_l2norm_weightnorm_vs_torch(ops):
     ops.l2norm_bwd(dout, out, inv, dz)
     keep = [i for i in range(37) if i != 5]
     assert rel(dz[keep], zd.grad[keep]) < 1e-5
+    assert rel(dz[5], dout[5].double() / 1e-12) < 1e-5              # below the clamp: dout / eps
     # weight_norm
     v, g = rnd(1024, 256, seed=9, scale=0.05), (1.0 + 0.1 * rnd(1024, seed=10))
     w, winv = torch.empty_like(v), torch.empty(1024, device=DEV)
