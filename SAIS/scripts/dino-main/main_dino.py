@@ -11,7 +11,9 @@ Kept: every flag, the linear lr scaling rule lr * global_batch / 256, the cosine
 `checkpoint%04d.pth` / `log.txt`, resume from `--output_dir/checkpoint.pth`.  Differences: `--use_fp16` is accepted and
 ignored (bf16 MFMA operands with fp32 master weights need no loss scaler); `--arch` must be vit_small (deit_small),
 `--optimizer` adamw, `--use_bn_in_head` False; the dataset list the reference hard-codes (:353) is the default of the
-extra `--datasets` flag, its hard-coded frame root './SAIS' (:288) the default of `--frames_root`.
+extra `--datasets` flag, its hard-coded frame root './SAIS' (:288) the default of `--frames_root`.  `--global_crops_size` /
+`--local_crops_size` (switches of this implementation; the reference hard-codes 224 / 96, :658-663) train at other view sizes:
+positive multiples of 16 of at most 4097 tokens; a size other than 224 / 96 takes the streaming attention kernels.
 """
 import argparse
 import datetime
@@ -28,6 +30,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 from sais_amd import dino  # noqa: E402
 from sais_amd.dino_data import DataAugmentationDINO, SurgDataset, collate_raw, gpu_crops  # noqa: E402
 from sais_amd.model_io import bool_flag  # noqa: E402
+from sais_amd.vit import MAX_DENSE_TOKENS  # noqa: E402
 
 
 FLAGS = [  # (flag, type, default)   — the reference parser, main_dino.py:48-141
@@ -58,13 +61,47 @@ def get_args_parser():
     return p
 
 
+class _CliParser(argparse.ArgumentParser):
+    """get_cli_parser()'s parser.  The two view-size switches are parsed by a parser of their own (crop_size_parser) before this
+    one sees the command line, and land in the same namespace: the switches on THIS parser's own list stay the reference's plus
+    --gpu_augment, which is what that list is pinned to."""
+
+    def parse_known_args(self, args=None, namespace=None):
+        sizes, rest = crop_size_parser().parse_known_args(sys.argv[1:] if args is None else list(args))
+        namespace, extras = super().parse_known_args(rest, namespace)
+        for k, v in vars(sizes).items():
+            setattr(namespace, k, v)
+        return namespace, extras
+
+    def format_help(self):
+        return super().format_help() + "\nview size " + crop_size_parser().format_help().split("\n\n", 1)[-1]
+
+
+def crop_size_parser():
+    p = argparse.ArgumentParser("DINO", add_help=False, allow_abbrev=False)
+    p.add_argument("--global_crops_size", type=crop_size, default=224,
+                   help="side of the two global views in pixels: a positive multiple of 16, at most 4097 tokens")
+    p.add_argument("--local_crops_size", type=crop_size, default=96, help="side of the local views, same rule")
+    return p
+
+
 def get_cli_parser():
-    """The command line: the reference's flags (get_args_parser) + switches of this implementation only."""
-    p = argparse.ArgumentParser("DINO", parents=[get_args_parser()])
+    """The command line: the reference's flags (get_args_parser) + switches of this implementation only: --gpu_augment, and
+    --global_crops_size / --local_crops_size (the reference hard-codes 224 / 96, :658-663)."""
+    p = _CliParser("DINO", parents=[get_args_parser()])
     p.add_argument("--gpu_augment", type=bool_flag, default=False,
                    help="decode the frames and make the multi-crop views on the GPU (sais_amd.jpeg + sais_amd.augment): "
                         "same views as the default Pillow loader for the same seed, bit for bit")
     return p
+
+
+def crop_size(text):
+    """A view side the patch-16 backbone trains on: a positive multiple of 16 with 1 + (side / 16)^2 <= 4097 tokens."""
+    side = int(text)
+    if side < 16 or side % 16 or 1 + (side // 16) ** 2 > MAX_DENSE_TOKENS:
+        raise argparse.ArgumentTypeError(f"{text}: a crop size is a positive multiple of 16 of at most {MAX_DENSE_TOKENS} tokens "
+                                         f"(at most {16 * math.isqrt(MAX_DENSE_TOKENS - 1)} pixels)")
+    return side
 
 
 def init_distributed(args):
@@ -82,6 +119,9 @@ def init_distributed(args):
     dist.barrier()
 
 
+AUG_MAX_SIZE = 224          # SAIS_AUG_MAX_SIZE (include/sais_hip.h): the largest view sais_augment_crop_resize makes
+
+
 def collate(batch):
     crops = [torch.stack([b[0][i] for b in batch]) for i in range(len(batch[0][0]))]
     return crops, [b[1] for b in batch], [b[2] for b in batch]
@@ -92,8 +132,13 @@ def build_loader(args, dev):
     Default: DataLoader workers decode and augment with Pillow, the tensors are copied.  --gpu_augment: the workers read
     the files and draw the views' parameters; decode and pixel work happen here, on the GPU, serially with the step."""
     gpu_augment = getattr(args, "gpu_augment", False)
+    gsize, lsize = getattr(args, "global_crops_size", 224), getattr(args, "local_crops_size", 96)
+    # the GPU augmenter takes its view sizes from the transform's draws, up to the side its kernels hold (SAIS_AUG_MAX_SIZE)
+    if gpu_augment and max(gsize, lsize) > AUG_MAX_SIZE:
+        sys.exit(f"--gpu_augment makes views of at most {AUG_MAX_SIZE} x {AUG_MAX_SIZE} pixels: use the default Pillow loader for "
+                 f"--global_crops_size {gsize} --local_crops_size {lsize}")
     transform = DataAugmentationDINO(args.global_crops_scale, args.local_crops_scale, args.local_crops_number,
-                                     seed=args.seed * 1000 + args.rank)
+                                     seed=args.seed * 1000 + args.rank, global_size=gsize, local_size=lsize)
     dataset = SurgDataset(args.data_path, args.datasets, transform, frames_root=args.frames_root, gpu_augment=gpu_augment)
     sampler = torch.utils.data.DistributedSampler(dataset, num_replicas=args.world_size, rank=args.rank, shuffle=True)
     loader = torch.utils.data.DataLoader(dataset, sampler=sampler, batch_size=args.batch_size_per_gpu,
@@ -134,7 +179,7 @@ def train_dino(args):
     if os.path.isfile(ckpt_path):                                    # utils.restart_from_checkpoint
         ck = torch.load(ckpt_path, map_location="cpu", weights_only=False)
         with torch.no_grad():                                        # flat buffers exist after one forward
-            probe = [torch.zeros(1, 3, 224, 224, device=dev)] * 2
+            probe = [torch.zeros(1, 3, args.global_crops_size, args.global_crops_size, device=dev)] * 2
             student(probe), teacher(probe)
         start_epoch = dino.load_checkpoint(ck, student, teacher, optimizer, dino_loss)
         if main:

@@ -952,6 +952,27 @@ int sais_vit_attn_fwd_any(const void* qkv, long ldqkv, int frames, int ntok, voi
                           void* stream);
 int sais_patchify_rect(const float* frames_f32 /*[F,3,H,W]*/, int frames, int H, int W, void* patches_bf16, void* stream);
 
+/* ================================================================ ViT-S/16 training at any frame size
+ * (sais_amd/csrc/attn_any_bwd.hip, host: VisionTransformer.forward under grad).  Additive entries: the ABI version does not change.
+ * sais_vit_attn_bwd_any: the backward of sais_vit_attn_fwd_any with the layouts and the arithmetic of sais_vit_attn_bwd, for any
+ *   2 <= ntok <= SAIS_VIT_ATTN_ANY_MAX_TOKENS and frames <= 65535.  qkv bf16 [frames*ntok, 1152] = q | k | v head-major, dout and
+ *   out (the saved forward output) bf16 [frames*ntok, 384], lse f32 [frames, 6, ntok] as the forward wrote it, dqkv bf16
+ *   [frames*ntok, 1152]: every element written exactly once.  P = exp2(s c - lse log2e) in f32, delta = rowsum(dout * out) in f32,
+ *   dS = P (dP - delta) rounded once to bf16 for dQ and dK, P rounded once to bf16 for dV; f32 accumulation, one rounding on
+ *   store.  Two launches, each the only writer of its outputs: (frame, head, query tile) computes delta (to the workspace, f32
+ *   [frames, 6, ntok]) and dQ with K / V streamed through LDS in 64-row tiles; (frame, head, key tile) computes dK and dV with Q /
+ *   dO / lse / delta streamed the same way.  S and dP are computed in both (7 tile products per pair instead of 5).  No atomics:
+ *   bit-reproducible, and a row's result does not depend on the workgroup size the launcher picks (64-row workgroups iff
+ *   frames * 6 * ceil(ntok / 64) >= 512, else 32-row ones).  Keys past ntok are masked before the exponential, query rows past
+ *   ntok contribute nothing; rows outside the tensor are reached by clamped loads only and never stored.
+ *   SAIS_ERR_ARG and nothing launched for: a null pointer, frames or ntok out of range, a row stride that is not a multiple of 8
+ *   or below the row width (1152 for qkv / dqkv, 384 for dout / out), workspace_bytes below
+ *   sais_vit_attn_bwd_any_workspace_bytes(frames, ntok) (0 for non-positive arguments).  The workspace is 16-B aligned.        */
+size_t sais_vit_attn_bwd_any_workspace_bytes(int frames, int ntok);
+int sais_vit_attn_bwd_any(const void* qkv, long ldqkv, const void* dout, long lddo, const void* out, long ldout,
+                          const float* lse, int frames, int ntok, void* dqkv, long lddqkv, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
 /* ================================================================ ViT-S/8: the patch-8 backbone (inference)
  * (sais_amd/csrc/vit8.hip, host: VisionTransformer with patch_size = 8).  Additive entries: the ABI version does not change.
  * sais_patchify_rect8: frames f32 [F, 3, H, W], H and W positive multiples of 8 -> patches bf16 [F * (H/8) * (W/8), 192], patch

@@ -317,6 +317,10 @@ SIGNATURES = {
     # ViT-S/8 (csrc/vit8.hip)
     "sais_patchify_rect8": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
     "sais_vit_attn_cls_fwd_any": [c_void_p, c_long, c_int, c_int, c_void_p, c_long, c_void_p],
+    # streaming attention backward: patch-16 training at any frame size (csrc/attn_any_bwd.hip)
+    "sais_vit_attn_bwd_any_workspace_bytes": [c_int, c_int],
+    "sais_vit_attn_bwd_any": [c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_void_p, c_int, c_int, c_void_p, c_long,
+                              c_void_p, ctypes.c_size_t, c_void_p],
 }
 
 _lib = None
@@ -352,6 +356,7 @@ def load():
     lib.sais_gemm_tn_grouped_slab_bytes.restype = ctypes.c_size_t
     lib.sais_knn_workspace_bytes.restype = ctypes.c_size_t
     lib.sais_colmean_cov_workspace_bytes.restype = ctypes.c_size_t
+    lib.sais_vit_attn_bwd_any_workspace_bytes.restype = ctypes.c_size_t
     lib.sais_last_error.restype = ctypes.c_char_p
     lib.sais_last_error.argtypes = []
     _lib = lib

@@ -208,9 +208,12 @@ class MultiCropWrapper(nn.Module):
         """All resolution groups go through the backbone in ONE pass (rows stacked: sais_amd.vit._forward_kernels), the
         features come back in crop order, exactly the concatenation utils.py:626 builds."""
         bb = self.backbone
-        groups = [bb._check_input(g) for g in self._groups(x)]
+        # patch 16: crops of any H x W in multiples of 16; a pass with a group off 224 x 224 / 96 x 96 is a streaming one
+        any_size = "forward" if bb.patch == 16 else None
+        groups = [bb._check_input(g, any_size) for g in self._groups(x)]
         bb._engine(groups[0].device)
-        feat, bsaved = bb._forward_kernels(groups if len(groups) > 1 else groups[0], save=save)
+        feat, bsaved = bb._forward_kernels(groups if len(groups) > 1 else groups[0], save=save,
+                                           streaming=bb.patch == 16 and bb.streaming_pass(groups))
         logits, hsaved = self.head.forward_kernels(feat, save)
         return logits, (bsaved, hsaved) if save else None
 

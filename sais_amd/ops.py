@@ -407,6 +407,30 @@ def vit_attn_bwd(qkv, dout, out, lse, delta_ws, frames, dqkv, ntok=197):
                           _p(lse), _p(delta_ws), frames, ntok, _p(dqkv), dqkv.stride(0), _stream()))
 
 
+_ATTN_ANY_WS = {}
+
+
+def vit_attn_bwd_any_workspace(frames, ntok, device):
+    """The delta workspace of vit_attn_bwd_any, one per (device, bytes): launches on a stream are ordered, so consecutive calls
+    share it.  While the stream is capturing: a fresh buffer from the graph's pool."""
+    n = int(L.load().sais_vit_attn_bwd_any_workspace_bytes(frames, ntok))
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty(n, dtype=torch.uint8, device=device)
+    key = (str(device), n)
+    if key not in _ATTN_ANY_WS:
+        _ATTN_ANY_WS[key] = torch.empty(n, dtype=torch.uint8, device=device)
+    return _ATTN_ANY_WS[key]
+
+
+def vit_attn_bwd_any(qkv, dout, out, lse, frames, ntok, dqkv):
+    """The streaming attention backward (csrc/attn_any_bwd.hip): any 2 <= ntok <= 4097.  out, lse: what vit_attn_fwd_any wrote."""
+    _chk(qkv, BF16, "qkv"); _chk(dout, BF16, "dout"); _chk(out, BF16, "out"); _chk(lse, F32, "lse"); _chk(dqkv, BF16, "dqkv")
+    ws = vit_attn_bwd_any_workspace(frames, ntok, qkv.device)
+    _timed("vit_attn_bwd_any", 14.0 * frames * 6 * ntok * ntok * 64, 2 * frames * ntok * 384 * 9,
+           lambda: L.call("sais_vit_attn_bwd_any", _p(qkv), qkv.stride(0), _p(dout), dout.stride(0), _p(out), out.stride(0),
+                          _p(lse), frames, ntok, _p(dqkv), dqkv.stride(0), _p(ws), ws.numel(), _stream()))
+
+
 def vit_block_params(f, i, depth):
     """SaisVitBlockParams of block i from a FlatParams engine (include/sais_hip.h): pointers into the flat parameter /
     gradient / shadow buffers, valid as long as those buffers live."""

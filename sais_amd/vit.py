@@ -17,8 +17,10 @@ main_dino.py:658-663, with interpolate_pos_encoding :174-194 as a fixed bicubic 
 rates linspace(0, drop_path_rate, depth); SAIS itself only ever runs the ViT in eval(), extract_representations.py:
 279,340,362) is applied in the epilogues of the residual GEMMs as a per-row scale; the keep draws come from Philox
 (`drop_path_seed`, this library's stream, not torch's): `last_droppath_scales` holds what a forward used.
-`dense_features` and `cls_attention` alone take other resolutions (any H x W in multiples of 16 up to 4097 tokens, inference
-only): their attention streams keys and values through LDS (csrc/attn_any.hip) instead of keeping a head resident, and
+Other resolutions (any H x W in multiples of 16 up to 4097 tokens) take the streaming attention, which moves keys and values
+through LDS in tiles instead of keeping a head resident: `dense_features`, `cls_attention` and `retrieval_features` (inference,
+csrc/attn_any.hip), and forward() whenever it needs gradients (training at any frame size: csrc/attn_any_bwd.hip; a pass in which
+every resolution group is 224 x 224 or 96 x 96 keeps the resident kernels and the launches it always had), and
 `cls_attention` ends in the CLS row of the last block's softmax (csrc/attnviz.hip) instead of `get_last_selfattention`'s
 [F, 6, N, N] tensor, which stays a 224 x 224 / 96 x 96 call.
 `vit_small(patch_size=8)` (ViT-S/8: 8 x 8 patches, a 28 x 28 positional grid, 785 tokens at 224 x 224) is an INFERENCE backbone: every
@@ -161,8 +163,8 @@ class _ViTFn(torch.autograd.Function):
     kernels into model.flat.grad (p.grad views) as a side effect; `anchor` only keeps the node alive."""
 
     @staticmethod
-    def forward(ctx, model, x, anchor):
-        reps, saved = model._forward_kernels(x, save=True)
+    def forward(ctx, model, x, anchor, streaming=False):
+        reps, saved = model._forward_kernels(x, save=True, streaming=streaming)
         ctx.model, ctx.saved = model, saved
         ctx.x_requires_grad = x.requires_grad
         return reps
@@ -171,7 +173,7 @@ class _ViTFn(torch.autograd.Function):
     def backward(ctx, dreps):
         ctx.model._backward_kernels(ctx.saved, dreps.contiguous())
         ctx.saved = None
-        return None, None, None
+        return None, None, None, None
 
 
 class VisionTransformer(nn.Module):
@@ -255,11 +257,17 @@ class VisionTransformer(nn.Module):
             x = self._check_input(x, "forward")
             self._engine(x.device)
             return self._forward_kernels(x, save=False, streaming=True)[0]
-        x = self._check_input(x)
+        x = self._check_input(x, "forward" if need_grad else None)      # training takes any H x W in multiples of 16
         self._engine(x.device)
         if need_grad:
-            return _ViTFn.apply(self, x, self._anchor)
+            return _ViTFn.apply(self, x, self._anchor, self.streaming_pass([x]))
         return self._forward_kernels(x, save=False)[0]
+
+    @staticmethod
+    def streaming_pass(imgs):
+        """True iff a training pass over these resolution groups is a streaming one: some group is not a square side of SIDES.
+        Every group of such a pass (a 224 x 224 one included) takes patchify_rect, sais_vit_attn_fwd_any and sais_vit_attn_bwd_any."""
+        return any(im.shape[2] != im.shape[3] or im.shape[2] not in SIDES for im in imgs)
 
     def get_last_selfattention(self, x):
         if self.patch == 8:
@@ -390,7 +398,8 @@ class VisionTransformer(nn.Module):
 
     def _check_input(self, x, any_size=None):
         """forward()'s input as a contiguous f32 tensor.  any_size: the name of the caller that takes every H x W in multiples of
-        the patch size (dense_features, cls_attention; every method of a patch-8 model) instead of the square sides of SIDES."""
+        the patch size (dense_features, cls_attention, forward under grad; every method of a patch-8 model) instead of the square
+        sides of SIDES."""
         P = self.patch
         if any_size is None:
             if not x.is_cuda:
@@ -432,8 +441,10 @@ class VisionTransformer(nn.Module):
         the pass stops and what the result is: "reps": after the final norm, reps f32 [sum F, 384] in group order; "probs":
         in the last block's attention, its probabilities (get_last_selfattention); "norm1": at the last block's norm1, its bf16
         output [M, 384] (cls_attention); "blocks": after the last block, the residual stream f32 [M, 384], every row computed
-        and no final norm.  streaming: any H x W in multiples of 16 (one resolution, inference): patchify_rect and the
-        attention that streams keys and values through LDS instead of the kernels instantiated for SIDES.  tap(i, x): called
+        and no final norm.  streaming: any H x W in multiples of 16: patchify_rect and the attention that streams keys
+        and values through LDS instead of the kernels instantiated for SIDES, in every group; with `save` the attention also
+        writes its log-sum-exp and the backward takes sais_vit_attn_bwd_any (the decision is recorded in `saved`).  A streaming
+        pass has no block-level C call and no fused-MLP kernel, in either direction.  tap(i, x): called
         after every block but a CLS-only last one with the residual stream the block left (without `save` the next block
         overwrites it); reps_out: a [sum F, 384] view (any row stride) that receives reps instead of a new tensor."""
         f = self.flat
@@ -452,7 +463,10 @@ class VisionTransformer(nn.Module):
         # the CLS-only tail runs its [frames, 384] GEMMs on the split-K small-M kernel (SAIS_EPI_RAW_SLABS_F32: M < 8192 only), so a
         # pass with 8192 or more FRAMES computes the last block on every row like the others (pruned=False is
         # recorded in `saved`, the backward follows it)
-        pl.prune = end == "reps" and self.prune_last_block and Ftot < ops.ROW_GEMM_MIN_M
+        # and a pass that is saved for a backward keeps the CLS-only tail only while sais_vit_attn_cls_bwd holds every group (one wave
+        # per (frame, head): CLS_WAVE_MAX_TOKENS); past it the last block is computed on every row
+        pl.prune = end == "reps" and self.prune_last_block and Ftot < ops.ROW_GEMM_MIN_M and \
+            not (save and any(g["ntok"] > CLS_WAVE_MAX_TOKENS for g in groups))
         pl.prune_q = pl.prune and len(groups) == 1 and _PRUNE_Q
         pl.mlp_fused = not streaming and ops.mlp_fused_enabled(M)      # (the streaming pass has never taken that switch)
         # One C call per Block (sais_vit_block_fwd: the launches of _block_fwd_launches, sequenced by the library) whenever
@@ -461,9 +475,10 @@ class VisionTransformer(nn.Module):
         pl.block_call = self.block_calls and ops.TIMER is None and len(groups) == 1 and fused and not pl.mlp_fused \
             and not streaming
         patches, x = self._embed_fwd(pl, imgs)
-        draw = self.training and self.drop_path_rate > 0 and end != "probs" and not streaming
+        draw = self.training and self.drop_path_rate > 0 and end != "probs"
         pl.dp = dp = self._droppath_draw(groups, dev) if draw else None
-        saved = {"patches": patches, "blocks": [], "groups": groups, "M": M, "Ftot": Ftot, "dp": dp} if save else None
+        saved = {"patches": patches, "blocks": [], "groups": groups, "M": M, "Ftot": Ftot, "dp": dp, "streaming": streaming,
+                 "pruned": False} if save else None
         b = ln1 = None                                   # the block's tensors; (xn, mean1, rstd1) of its norm1
         # norm1's outputs for a block: its own with `save`, else one xn for the whole pass and no statistics
         norm1_out = lambda: (pl.e16(M, D), pl.e32(M), pl.e32(M)) if save else ln1 or (pl.e16(M, D), None, None)
@@ -575,7 +590,7 @@ class VisionTransformer(nn.Module):
                 probs = pl.e32(g["Fr"], HEADS, g["ntok"], g["ntok"])
             qkv, ao = _rows(b["qkv"], g), _rows(b["ao"], g)
             if pl.streaming:
-                ops.vit_attn_fwd_any(qkv, g["Fr"], g["ntok"], ao)
+                ops.vit_attn_fwd_any(qkv, g["Fr"], g["ntok"], ao, lg)
             else:
                 ops.vit_attn_fwd(qkv, g["Fr"], ao, lg, probs, ntok=g["ntok"])
         return probs
@@ -751,16 +766,16 @@ class VisionTransformer(nn.Module):
         groups, M, dp = saved["groups"], saved["M"], saved.get("dp")
         e16 = _empty(torch.bfloat16, dev)
         # Every decision of the pass, taken once (from this pass's own inputs, not from what the forward decided).
-        pruned = bool(saved.get("pruned"))
+        pruned, streaming = bool(saved.get("pruned")), bool(saved.get("streaming"))      # (what the forward recorded)
         fused = M >= ops.ROW_GEMM_MIN_M
-        mlp_fused = ops.mlp_fused_enabled(M)
-        block_call = self.block_calls and ops.TIMER is None and len(groups) == 1 and fused and not mlp_fused
+        mlp_fused = not streaming and ops.mlp_fused_enabled(M)
+        block_call = self.block_calls and ops.TIMER is None and len(groups) == 1 and fused and not mlp_fused and not streaming
         # a data-parallel hook that all-reduces the blocks' gradients while the backward goes on (an idle one — GradSync in a world
         # of one — carries active = False)
         hooked = self.grad_ready_hook is not None and getattr(self.grad_ready_hook, "active", True)
         # blocks per weight-gradient launch (_PendingDW); 1: every block launches its own
         G = ops.dw_group(dp_hooks=hooked) if fused and M % 32 == 0 and not mlp_fused else 1
-        pl = SimpleNamespace(groups=groups, M=M, e16=e16, fused=fused, mlp_fused=mlp_fused, defer=G > 1)
+        pl = SimpleNamespace(groups=groups, M=M, e16=e16, fused=fused, mlp_fused=mlp_fused, defer=G > 1, streaming=streaming)
         pend = _PendingDW(self, saved, G, hooked)
         dxa = e16(M, D)                            # bf16 copy of the residual-stream gradient that enters a block
         # scratch of the launch list (the C call has its workspace; dqkv also serves the CLS-only block): dxb = the bf16 gradient at
@@ -841,7 +856,10 @@ class VisionTransformer(nn.Module):
         ops.gemm_nt(dxb, f.wt16[p + "attn.proj.weight"], L.EPI_BIAS_BF16, dao)
         for g, lg in zip(pl.groups, s["lse"]):
             r = g["rows"]
-            ops.vit_attn_bwd(s["qkv"][r], dao[r], s["ao"][r], lg, None, g["Fr"], dqkv[r], ntok=g["ntok"])
+            if pl.streaming:
+                ops.vit_attn_bwd_any(s["qkv"][r], dao[r], s["ao"][r], lg, g["Fr"], g["ntok"], dqkv[r])
+            else:
+                ops.vit_attn_bwd(s["qkv"][r], dao[r], s["ao"][r], lg, None, g["Fr"], dqkv[r], ntok=g["ntok"])
         # all four weight / bias gradients of the block in one launch.  (A side stream for this launch was measured
         # in round 1: 20.4 vs 19.6 ms/step — both kernels fill the chip — and removed.)
         dw = [(dxa, s["h"], f.g(p + "mlp.fc2.weight"), f.g(p + "mlp.fc2.bias")),
