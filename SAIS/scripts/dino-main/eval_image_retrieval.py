@@ -17,7 +17,9 @@ exits, as eval_knn.py here); `--dist_url` / `--local_rank` / `--use_cuda` are ac
 similarities rank in ascending database index; `--dump_features <dir>` (new) saves the normalised features;
 `--gpu_loader true` (new) decodes the files and makes the thumbnails on the GPU (sais_amd/imgfolder.py: the workers only read
 the files, `--gpu_loader_batch` of them per decode call), bit-identical to the Pillow loader's, and `--group_shapes true` (new,
-with `--gpu_loader true` only) hands the thumbnails of one such batch that share a shape to the backbone together.
+with `--gpu_loader true` only) hands the thumbnails of one such batch that share a shape to the backbone together;
+`--mixed_batch true` (new, with `--gpu_loader true` only, patch 16, not with `--group_shapes true`) hands ALL thumbnails of one
+such batch to the backbone in one segmented pass, whatever their shapes.
 """
 import argparse
 import os
@@ -55,6 +57,9 @@ def get_args_parser():
     parser.add_argument('--group_shapes', default=False, type=bool_flag,
                         help="""With --gpu_loader true: thumbnails of one loader batch that share a shape go through the
         backbone together instead of one by one.""")
+    parser.add_argument('--mixed_batch', default=False, type=bool_flag,
+                        help="""With --gpu_loader true: all thumbnails of one loader batch, whatever their shapes, go through
+        the backbone in one segmented pass (patch 16 only; not together with --group_shapes true).""")
     return parser
 
 
@@ -62,6 +67,12 @@ def main(argv=None):
     args = get_args_parser().parse_args(argv)
     if args.group_shapes and not args.gpu_loader:
         sys.exit("--group_shapes true needs --gpu_loader true: the Pillow loader yields one image per batch")
+    if args.mixed_batch and not args.gpu_loader:
+        sys.exit("--mixed_batch true needs --gpu_loader true: the Pillow loader yields one image per batch")
+    if args.mixed_batch and args.group_shapes:
+        sys.exit("--mixed_batch true and --group_shapes true exclude each other: choose one way to batch the thumbnails")
+    if args.mixed_batch and args.patch_size != 16:
+        sys.exit("--mixed_batch true runs on --patch_size 16 only: the segmented pass is not built for patch 8")
     if args.gpu_loader_batch < 1:
         sys.exit("--gpu_loader_batch must be at least 1")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -80,7 +91,7 @@ def main(argv=None):
         dataset_query = imgfolder.RawOxfordParis(args.data_path, args.dataset, split="query")
         loader = lambda ds: retrieval.ThumbnailBatches(torch.utils.data.DataLoader(
             ds, batch_size=args.gpu_loader_batch, num_workers=args.num_workers, drop_last=False, shuffle=False,
-            collate_fn=imgfolder.collate_raw), gpu_loader, args.imsize, args.group_shapes)
+            collate_fn=imgfolder.collate_raw), gpu_loader, args.imsize, args.group_shapes, mixed=args.mixed_batch)
     else:
         dataset_train = retrieval.OxfordParisDataset(args.data_path, args.dataset, split="train", imsize=args.imsize)
         dataset_query = retrieval.OxfordParisDataset(args.data_path, args.dataset, split="query", imsize=args.imsize)

@@ -1087,6 +1087,55 @@ int sais_center_rows(float* x, long ldx, long rows, int dim, const float* mean, 
 int sais_rank_positions(const float* sim, long ld, int Nq, int Ndb, const int* offsets, const int* items, int* pos, void* stream);
 int sais_resize_bilinear_f32(const float* x, int frames, int H, int W, double scale, float* y, int Ho, int Wo, void* stream);
 
+/* ================================================================ frames of different sizes in one backbone pass (inference)
+ * (sais_amd/csrc/attn_seg.hip, host: sais_amd/vit_seg.py and VisionTransformer.retrieval_features / dense_features on a list).
+ * Additive entries: the ABI version does not change.  Patch 16 only.  No atomics: every entry is bit-reproducible.
+ * A pass is described by one table with one sais_vit_seg record per FRAME (a segment of the stacked [M, .] token rows):
+ *   row0: its first token row; ntok = 1 + gh * gw tokens (2 .. SAIS_VIT_ATTN_ANY_MAX_TOKENS), gh x gw its patch grid; pix: the
+ *   offset in floats of its pixels [3, 16 gh, 16 gw] (contiguous) in a packed f32 buffer, a multiple of 4; tap_y / tap_x: the
+ *   offsets in floats of its two per-axis interpolation matrices f32 [gh, 14] and [gw, 14] in a tap buffer (the rows of
+ *   interpolate_pos_encoding's bicubic map along one axis, vision_transformer.py:174-194; a matrix depends on the grid side
+ *   alone and is shared by every segment with that side), or both -1 for a 14 x 14 grid, which takes the positional table itself.
+ * Every entry takes the table twice: the host copy is what the argument checks read, the device copy (16-B aligned) what the kernel
+ * reads; they must hold the same records.  Segments are in ascending row order and do not overlap; `rows` is the number of rows
+ * the stacked tensors have (rows past the last segment are never touched).  The entries marked "dense" need row0 of segment s
+ * = the sum of ntok of the segments before it (stacked from row 0 without gaps).
+ * SAIS_ERR_ARG and nothing launched for: a null table, nseg outside 1 .. 65535, a record out of these ranges, a misaligned or
+ * too small row stride, and what each entry adds below.
+ * sais_vit_seg_qtile: the queries per workgroup sais_vit_attn_fwd_seg uses for these segments, 64 or 32: the rule of
+ *   sais_vit_attn_fwd_any applied to the pass (64 iff 6 * sum ceil(ntok / 64) >= 512).  Host only, reads ntok.
+ * sais_vit_attn_fwd_seg: the streaming attention forward over all segments in ONE launch.  qkv bf16 [rows, 1152] (row stride ldqkv
+ *   >= 1152, a multiple of 8), out bf16 [rows, 384] (ldo >= 384, a multiple of 4), lse f32 [6 * rows] or NULL: segment s owns
+ *   lse[6 row0 .. 6 (row0 + ntok)) as [6, ntok].  tiles: ntiles (segment, first query) pairs of int32, one per workgroup, in any
+ *   order, covering the queries of every segment in steps of qtile = sais_vit_seg_qtile(...) exactly once — ntiles must equal
+ *   sum ceil(ntok / qtile) and every pair must lie inside its segment (checked on the host copy; 8-B aligned on the device).
+ *   Contract: the bytes written for segment s equal what sais_vit_attn_fwd_any(frames = 1, ntok) writes for
+ *   (qkv + row0 ldqkv, out + row0 ldo, lse + 6 row0), in either workgroup form: both kernels run one tile body
+ *   (csrc/attn_stream.hpp), in which a query's result depends on the rows of its own frame alone.
+ * sais_patchify_seg (dense): pixels f32 [npix] packed -> patches bf16 [sum gh gw, 768] in segment order; per segment bit-equal
+ *   to sais_patchify_rect on that frame.  A segment whose pixels do not lie inside [0, npix) is SAIS_ERR_ARG.
+ * sais_vit_embed_seg (dense): x f32 [rows, 384] token rows of every segment: row0 = cls + pos[0]; row0 + 1 + p = patch_out[row0 -
+ *   s + p] + the positional row of patch p, where patch_out f32 [sum gh gw, 384] is the patch GEMM's output with its bias, pos f32
+ *   [197, 384] the positional table and the positional row of patch (y, x) is sum_a Ty[y][a] (sum_b Tx[x][b] pos[1 + 14 a + b])
+ *   over the non-zero taps in ascending order (f32, at most sixteen terms).  taps f32 [ntaps]; a matrix outside it is SAIS_ERR_ARG.
+ * sais_vit_cls_gather_seg: out f32 [nseg, 384] = x[row0 of every segment] (x f32, row stride ldx >= 384, a multiple of 4): the
+ *   input of the sais_layernorm_fwd launch that makes the features.                                                            */
+typedef struct sais_vit_seg {
+    int row0, ntok, gh, gw;
+    long long pix;
+    int tap_y, tap_x;
+} sais_vit_seg;
+int sais_vit_seg_qtile(const sais_vit_seg* segs_host, int nseg);
+int sais_vit_attn_fwd_seg(const void* qkv, long ldqkv, long rows, const sais_vit_seg* segs_host, const sais_vit_seg* segs_dev,
+                          int nseg, const int* tiles_host, const int* tiles_dev, int ntiles, void* out, long ldo, float* lse,
+                          void* stream);
+int sais_patchify_seg(const float* pixels_f32, long npix, const sais_vit_seg* segs_host, const sais_vit_seg* segs_dev, int nseg,
+                      void* patches_bf16, void* stream);
+int sais_vit_embed_seg(const float* patch_out, const float* cls, const float* pos, const float* taps_dev, long ntaps,
+                       const sais_vit_seg* segs_host, const sais_vit_seg* segs_dev, int nseg, float* x, long rows, void* stream);
+int sais_vit_cls_gather_seg(const float* x, long ldx, long rows, const sais_vit_seg* segs_host, const sais_vit_seg* segs_dev,
+                            int nseg, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -116,6 +116,11 @@ class SaisImgXform(ctypes.Structure):
                 ("out_offset", ctypes.c_int64)]
 
 
+class SaisVitSeg(ctypes.Structure):                    # sais_vit_seg: one frame of a mixed-size pass (csrc/attn_seg.hip)
+    _fields_ = [("row0", c_int), ("ntok", c_int), ("gh", c_int), ("gw", c_int), ("pix", ctypes.c_int64), ("tap_y", c_int),
+                ("tap_x", c_int)]
+
+
 OP_VIT_BLOCK_FWD, OP_VIT_BLOCK_BWD, OP_TEMPORAL_LAYER_FWD, OP_TEMPORAL_LAYER_BWD = 0, 1, 2, 3
 
 
@@ -321,6 +326,13 @@ SIGNATURES = {
     "sais_vit_attn_bwd_any_workspace_bytes": [c_int, c_int],
     "sais_vit_attn_bwd_any": [c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_void_p, c_int, c_int, c_void_p, c_long,
                               c_void_p, ctypes.c_size_t, c_void_p],
+    # frames of different sizes in one pass (csrc/attn_seg.hip)
+    "sais_vit_seg_qtile": [c_void_p, c_int],
+    "sais_vit_attn_fwd_seg": [c_void_p, c_long, c_long, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_long,
+                              c_void_p, c_void_p],
+    "sais_patchify_seg": [c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
+    "sais_vit_embed_seg": [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p, c_long, c_void_p],
+    "sais_vit_cls_gather_seg": [c_void_p, c_long, c_long, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
 }
 
 _lib = None

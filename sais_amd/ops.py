@@ -375,6 +375,45 @@ def vit_attn_fwd_any(qkv, frames, ntok, out, lse=None):
                           _stream()))
 
 
+def vit_attn_fwd_seg(qkv, plan, out, lse=None):
+    """The streaming attention forward over every segment of a mixed-size pass in one launch (csrc/attn_seg.hip); plan: a
+    vit_seg.SegPlan on the device.  lse f32 [6 * rows]: segment s owns [6, ntok] at 6 * row0."""
+    _chk(qkv, BF16, "qkv"); _chk(out, BF16, "out"); _chk(lse, F32, "lse")
+    rows = min(qkv.shape[0], out.shape[0])
+    if lse is not None and lse.numel() < 6 * plan.M:
+        raise L.SaisHipError("lse: expected 6 floats per stacked row")
+    sq = sum(n * n for n in plan.ntoks)
+    _timed("vit_attn_fwd_seg", 4.0 * 6 * sq * 64, 2 * plan.M * 384 * 4,
+           lambda: L.call("sais_vit_attn_fwd_seg", _p(qkv), qkv.stride(0), rows, plan.segs_host, plan.segs_dev, plan.nseg,
+                          plan.tiles_host, plan.tiles_dev, plan.ntiles, _p(out), out.stride(0), _p(lse), _stream()))
+
+
+def patchify_seg(pixels, plan, patches):
+    """Packed pixels f32 [plan.npix] (frame s = [3, 16 gh, 16 gw] at its record's offset) -> bf16 [plan.NP, 768] in segment order."""
+    _chk(pixels, F32, "pixels"); _chk(patches, BF16, "patches")
+    if not patches.is_contiguous() or patches.numel() < plan.NP * 768:
+        raise L.SaisHipError(f"patches: expected a contiguous [{plan.NP}, 768] tensor")
+    L.call("sais_patchify_seg", _p(pixels), pixels.numel(), plan.segs_host, plan.segs_dev, plan.nseg, _p(patches), _stream())
+
+
+def vit_embed_seg(patch_out, cls, pos, plan, x):
+    """Token rows of every segment: CLS + pos[0] | patch_out (the patch GEMM with its bias, f32 [plan.NP, 384]) + the positional
+    table interpolated to the segment's grid -> x f32 [>= plan.M, 384]."""
+    _chk(patch_out, F32, "patch_out"); _chk(x, F32, "x"); _chk(pos, F32, "pos"); _chk(cls, F32, "cls")
+    if not (patch_out.is_contiguous() and x.is_contiguous()) or patch_out.numel() < plan.NP * 384 or pos.numel() < 197 * 384:
+        raise L.SaisHipError("vit_embed_seg: expected contiguous patch_out [NP, 384], x [M, 384] and pos [197, 384]")
+    L.call("sais_vit_embed_seg", _p(patch_out), _p(cls), _p(pos), plan.taps_dev, plan.ntaps, plan.segs_host, plan.segs_dev,
+           plan.nseg, _p(x), x.shape[0], _stream())
+
+
+def vit_cls_gather_seg(x, plan, out):
+    """out f32 [plan.nseg, 384] = the CLS row of every segment of x f32 [rows, 384]."""
+    _chk(x, F32, "x"); _chk(out, F32, "out")
+    if not out.is_contiguous() or out.numel() < plan.nseg * 384:
+        raise L.SaisHipError(f"out: expected a contiguous [{plan.nseg}, 384] tensor")
+    L.call("sais_vit_cls_gather_seg", _p(x), x.stride(0), x.shape[0], plan.segs_host, plan.segs_dev, plan.nseg, _p(out), _stream())
+
+
 def vit_cls_probs(q, k, frames, ntok, probs):
     """Row 0 of the last block's softmax (csrc/attnviz.hip): q bf16 [frames, 384] (the CLS queries), k bf16 [frames*ntok, 384]
     (row stride free: the K third of a qkv buffer in place) -> probs f32 [frames, 6, ntok] over all ntok keys."""

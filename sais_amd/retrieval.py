@@ -85,7 +85,13 @@ def multi_scale(samples, model):
     """utils.multi_scale (utils.py:816-830): the mean of model(.) over the scales 1, 1/sqrt(2), 1/2 of `samples`, divided by the
     norm of the WHOLE result tensor, as the reference does.  Each scale is cropped to multiples of the patch size (model.patch
     where the callable carries it, as those of cls_features / descriptor_features do; else 16) before `model` sees it.
-    model: a callable on device frames f32 [F, 3, H, W] (`cls_features(vit)` for the retrieval evaluation)."""
+    model: a callable on device frames f32 [F, 3, H, W] (`cls_features(vit)` for the retrieval evaluation).
+    samples a LIST of such tensors of different sizes (model must take a list: cls_features on a patch-16 backbone): all three
+    scales of all items go through the backbone in ONE call (3 n items); row block i of the result is the mean over the scales
+    of item i divided by the norm of that block alone, which is what the reference computes at its batch size of 1 (the
+    whole-batch norm of the stacked form does not appear).  The two rescaling launches per item stay per item."""
+    if isinstance(samples, (list, tuple)):
+        return _multi_scale_list(samples, model)
     if not isinstance(samples, torch.Tensor) or not samples.is_cuda:
         raise L.SaisHipError("multi_scale: expected a device tensor (no CPU fallback)")
     frames = samples.float().contiguous()
@@ -95,11 +101,35 @@ def multi_scale(samples, model):
     return mean / mean.norm()
 
 
+def _multi_scale_list(samples, model):
+    if len(samples) == 0:
+        raise ValueError("multi_scale: an empty list of frames")
+    patch = getattr(model, "patch", PATCH)
+    views = []
+    for x in samples:
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise L.SaisHipError("multi_scale: expected device tensors (no CPU fallback)")
+        frames = x.float().contiguous()
+        views += [crop_to_patches(frames if s == 1 else resize_bilinear(frames, s), patch) for s in SCALES]
+    feats = model(views)                                  # [sum over items of 3 F_i, D], item-major, scale, frame
+    out, row = torch.empty(sum(x.shape[0] for x in samples), feats.shape[1], dtype=torch.float32, device=feats.device), 0
+    for i, x in enumerate(samples):
+        Fr = x.shape[0]
+        mean = feats[3 * row:3 * (row + Fr)].view(len(SCALES), Fr, -1).sum(0) / len(SCALES)
+        out[row:row + Fr] = mean / mean.norm()
+        row += Fr
+    return out
+
+
 def cls_features(vit):
     """model(x) of the reference at any resolution: the CLS token of the final norm, f32 [F, 384] (the first half of
     retrieval_features, bit for bit), of the frames cropped to whole patches.  Only the final LayerNorm of the CLS rows runs
-    after the blocks: the GeM pass over the patch rows is not computed."""
-    fn = lambda x: vit.retrieval_features(crop_to_patches(x, fn.patch), cls_only=True)
+    after the blocks: the GeM pass over the patch rows is not computed.  A list of frames of different sizes goes through the
+    backbone in one segmented pass (VisionTransformer.retrieval_features on a list): f32 [sum F, 384] in list order."""
+    def fn(x):
+        if isinstance(x, (list, tuple)):
+            return vit.retrieval_features([crop_to_patches(t, fn.patch) for t in x], cls_only=True)
+        return vit.retrieval_features(crop_to_patches(x, fn.patch), cls_only=True)
     fn.patch = vit.patch_embed.patch_size
     return fn
 
@@ -408,10 +438,15 @@ class ThumbnailBatches:
     the order of their first image; extract_features scatters the rows by index.  A backbone call on F frames computes
     each row as it computes it alone up to the rounding of its kernels' batch-dependent tiling; under multi_scale the
     result is also divided by the norm of the WHOLE batch tensor, a scalar per call that the row normalisation after
-    extract_features (l2_normalize) removes up to rounding."""
+    extract_features (l2_normalize) removes up to rounding.  With mixed every loader batch is ONE item: (the list of its
+    thumbnails [1, 3, h_k, w_k], index [F]), for a backbone callable that takes frames of different sizes in one segmented pass
+    (cls_features on a patch-16 model, multi_scale over it)."""
 
-    def __init__(self, loader, gpu_loader, imsize, group_shapes=False):
+    def __init__(self, loader, gpu_loader, imsize, group_shapes=False, mixed=False):
+        if group_shapes and mixed:
+            raise ValueError("ThumbnailBatches: group_shapes and mixed exclude each other")
         self.loader, self.gpu_loader, self.imsize, self.group_shapes = loader, gpu_loader, int(imsize), bool(group_shapes)
+        self.mixed = bool(mixed)
         self.dataset = loader.dataset
 
     def __len__(self):
@@ -420,6 +455,9 @@ class ThumbnailBatches:
     def __iter__(self):
         for items, tags in self.loader:
             thumbs = self.gpu_loader.thumbnail(items, self.imsize)
+            if self.mixed:
+                yield list(thumbs), tags
+                continue
             if not self.group_shapes:
                 for k, t in enumerate(thumbs):
                     yield t, tags[k:k + 1]
@@ -435,10 +473,15 @@ class ThumbnailBatches:
 def extract_features(fn, loader, device="cuda:0"):
     """Features [N, D] on the device in dataset order; `loader` yields (images, dataset indices), fn maps device frames to [F, D]
     (cls_features, descriptor_features, or multi_scale over one of them: each crops to whole patches itself, multi_scale after
-    rescaling the uncropped frame as the reference does)."""
+    rescaling the uncropped frame as the reference does).  An item whose images are a LIST of frames of different sizes
+    (ThumbnailBatches(mixed=True)) is handed to fn as a list."""
     feats = None
     for samples, index in loader:
-        out = fn(samples.to(device, non_blocking=True)).float()
+        if isinstance(samples, (list, tuple)):
+            samples = [t.to(device, non_blocking=True) for t in samples]
+        else:
+            samples = samples.to(device, non_blocking=True)
+        out = fn(samples).float()
         if feats is None:
             feats = torch.zeros(len(loader.dataset), out.shape[-1], dtype=torch.float32, device=device)
         feats.index_copy_(0, index.to(device), out)

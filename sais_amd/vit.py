@@ -39,6 +39,7 @@ import torch.nn as nn
 from . import _lib as L
 from . import ops
 from .flat import ensure_flat
+from .vit_seg import SegPlan
 
 D, NTOK, HEADS, HID, PATCH_K = 384, 197, 6, 1536, 768
 _PRUNE_Q = os.environ.get("SAIS_VIT_PRUNE_Q", "1") != "0"     # the CLS-only last block computes q for the CLS rows only
@@ -57,25 +58,29 @@ def _cubic_taps(t, A=-0.75):
     return np.stack([far(t + 1), near(t), near(1 - t), far(2 - t)], axis=1)
 
 
+def pos_axis_matrix(side_in, n0):
+    """interpolate_pos_encoding (vision_transformer.py:174-194) along one axis, f64 [n0, side_in]: F.interpolate(scale_factor=
+    (n0 + 0.1) / side_in, mode='bicubic', align_corners=False) samples at (dst + 0.5) / scale - 0.5 with border-clamped taps
+    (clamped taps add up)."""
+    scale = (n0 + 0.1) / side_in
+    n_out = int(math.floor(side_in * scale))
+    if n_out != n0:
+        raise ValueError(f"interpolate_pos_encoding: {n_out} != {n0} (vision_transformer.py:191)")
+    x = (np.arange(n_out) + 0.5) / scale - 0.5
+    x0 = np.floor(x)
+    taps = _cubic_taps(x - x0)
+    M = np.zeros((n_out, side_in))
+    for k in range(4):
+        idx = np.clip(x0.astype(np.int64) + k - 1, 0, side_in - 1)
+        np.add.at(M, (np.arange(n_out), idx), taps[:, k])
+    return M
+
+
 def pos_interp_matrix(side_in, w, h, patch=16):
     """interpolate_pos_encoding (vision_transformer.py:174-194) as a matrix: [w0 * h0, side_in^2] with
-    patch_pos(w, h) = M @ patch_pos(224).  Per axis: F.interpolate(scale_factor=(n0 + 0.1) / side_in, mode='bicubic',
-    align_corners=False) samples at (dst + 0.5) / scale - 0.5 with border-clamped taps; the 2-D map is their Kronecker
-    product (first axis = the first index of the 14 x 14 grid)."""
-    def axis(n0):
-        scale = (n0 + 0.1) / side_in
-        n_out = int(math.floor(side_in * scale))
-        if n_out != n0:
-            raise ValueError(f"interpolate_pos_encoding: {n_out} != {n0} (vision_transformer.py:191)")
-        x = (np.arange(n_out) + 0.5) / scale - 0.5
-        x0 = np.floor(x)
-        taps = _cubic_taps(x - x0)
-        M = np.zeros((n_out, side_in))
-        for k in range(4):
-            idx = np.clip(x0.astype(np.int64) + k - 1, 0, side_in - 1)
-            np.add.at(M, (np.arange(n_out), idx), taps[:, k])
-        return M
-    return np.kron(axis(w // patch), axis(h // patch))
+    patch_pos(w, h) = M @ patch_pos(224): the Kronecker product of the two per-axis maps (pos_axis_matrix; first axis = the
+    first index of the 14 x 14 grid)."""
+    return np.kron(pos_axis_matrix(side_in, w // patch), pos_axis_matrix(side_in, h // patch))
 
 
 class _Attention(nn.Module):
@@ -349,8 +354,48 @@ class VisionTransformer(nn.Module):
         launch list of forward() (_forward_kernels) with `streaming`: patchify_rect, the patch GEMM with the positional table
         interpolated to (H, W) (interpolate_pos_encoding :174-194), then per block the row-generic GEMM / LayerNorm kernels
         around the streaming attention (sais_vit_attn_fwd_any).  A 224 x 224 input takes these kernels too
-        (dino-main/eval_video_segmentation.py runs it at 480 x 832: 1561 tokens)."""
+        (dino-main/eval_video_segmentation.py runs it at 480 x 832: 1561 tokens).
+        x a LIST or tuple of such tensors [F_i, 3, H_i, W_i] of different sizes (patch 16 only): ONE segmented pass over all
+        frames (every frame a segment of the stacked rows: sais_patchify_seg, the patch GEMM, sais_vit_embed_seg, then per block
+        the same row-generic launches around one sais_vit_attn_fwd_seg, csrc/attn_seg.hip), whose launch list does not depend on
+        the number of frames or shapes.  Returns per requested layer a list of [F_i, 1 + hw_i, 384] views.  The checks and
+        error texts are the single tensor's, per item; an empty list raises."""
+        if isinstance(x, (list, tuple)):
+            return self._dense_features_list(x, n)
         return self._last_norms(self._check_input(x, "dense_features"), n, streaming=True)
+
+    def _check_list(self, items, name):
+        """A list of device tensors [F_i, 3, H_i, W_i] for one segmented pass: _check_input per item, with its errors."""
+        if self.patch != 16:
+            raise NotImplementedError(f"VisionTransformer.{name} on a list of frames of different sizes is a patch-16 pass: a "
+                                      "patch-8 model takes one tensor per call")
+        if len(items) == 0:
+            raise ValueError(f"VisionTransformer.{name}: an empty list of frames")
+        return [self._check_input(x, name) for x in items]
+
+    def _dense_features_list(self, items, n):
+        """dense_features on a list: one segmented pass; per requested layer a list of [F_i, 1 + hw_i, 384] views of one
+        stacked tensor."""
+        items = self._check_list(items, "dense_features")
+        n = int(n)
+        if not 1 <= n <= self.depth:
+            raise ValueError(f"n = {n} must be in [1, {self.depth}]")
+        f, out = self._engine(items[0].device), []
+        groups = _row_groups(items, self.patch)[0]
+
+        def tap(i, xs):
+            if i >= self.depth - n:
+                y = torch.empty(xs.shape[0], D, dtype=torch.float32, device=xs.device)
+                ops.layernorm_fwd(xs, xs.shape[0], D, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6, y32=y)
+                out.append([y[g["rows"]].view(g["Fr"], g["ntok"], D) for g in groups])
+        self._forward_kernels(items, save=False, end="blocks", tap=tap, streaming=True, seg=self._seg_plan(items))
+        return out
+
+    @staticmethod
+    def _seg_plan(items):
+        """The SegPlan of a pass over these items on their device (one pinned copy): one segment per frame, in list order."""
+        grids = [(im.shape[2] // 16, im.shape[3] // 16) for im in items for _ in range(im.shape[0])]
+        return SegPlan(grids).to_device(items[0].device)
 
     @torch.no_grad()
     def retrieval_features(self, x, cls_only=False):
@@ -360,7 +405,25 @@ class VisionTransformer(nn.Module):
         interleaved.  Inference only.  Launches: dense_features' for every block, then sais_vit_cls_gem_norm on the residual
         stream: the normed [F, N, 384] tensor is never written.  cls_only: f32 [F, 384], the first half alone (what
         eval_image_retrieval.py reads: model(x) at any resolution) — the blocks, then one sais_layernorm_fwd launch over the CLS
-        rows, which is the launch that writes the first half of the full descriptor, so the bits are the same; no GeM pass."""
+        rows, which is the launch that writes the first half of the full descriptor, so the bits are the same; no GeM pass.
+        x a LIST or tuple of tensors [F_i, 3, H_i, W_i] of different sizes (patch 16, cls_only=True only; the GeM half over
+        segments is not built): one segmented pass as dense_features runs it on a list, then sais_vit_cls_gather_seg and the
+        same sais_layernorm_fwd launch over the gathered CLS rows: f32 [sum F_i, 384] in list order.  A frame's row agrees with
+        the single-tensor call up to the rounding of the batch-dependent GEMM tiling and of the separable positional
+        interpolation (sixteen f32 terms instead of one f32 GEMM row)."""
+        if isinstance(x, (list, tuple)):
+            # frames of different sizes: one segmented pass, then the CLS rows gathered for the same sais_layernorm_fwd launch
+            items = self._check_list(x, "retrieval_features")
+            if not cls_only:
+                raise NotImplementedError("retrieval_features on a list returns the CLS half only (cls_only=True): the GeM "
+                                          "pooling over segments of different sizes is not built")
+            f, seg = self._engine(items[0].device), self._seg_plan(items)
+            xs = self._forward_kernels(items, save=False, end="blocks", streaming=True, seg=seg)[0]
+            cls = torch.empty(seg.nseg, D, dtype=torch.float32, device=xs.device)
+            feats = torch.empty_like(cls)
+            ops.vit_cls_gather_seg(xs, seg, cls)
+            ops.layernorm_fwd(cls, seg.nseg, D, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6, y32=feats)
+            return feats
         x = self._check_input(x, "retrieval_features")
         f, Fr = self._engine(x.device), x.shape[0]
         xs = self._forward_kernels(x, save=False, end="blocks", streaming=True)[0]
@@ -433,7 +496,7 @@ class VisionTransformer(nn.Module):
         return out, Wm
 
     # ------------------------------------------------------------------ forward kernels
-    def _forward_kernels(self, img, save, end="reps", tap=None, reps_out=None, streaming=False):
+    def _forward_kernels(self, img, save, end="reps", tap=None, reps_out=None, streaming=False, seg=None):
         """img: one [F,3,H,W] tensor, or a LIST of them with different sizes (DINO's multi-crop student, utils.py:611-630):
         the groups are then stacked along the token-row axis and every GEMM / LayerNorm of a block runs ONCE over all rows
         (only attention, the embedding glue and the final CLS gather are per group) — 44 160 rows in one launch fill the
@@ -446,7 +509,10 @@ class VisionTransformer(nn.Module):
         writes its log-sum-exp and the backward takes sais_vit_attn_bwd_any (the decision is recorded in `saved`).  A streaming
         pass has no block-level C call and no fused-MLP kernel, in either direction.  tap(i, x): called
         after every block but a CLS-only last one with the residual stream the block left (without `save` the next block
-        overwrites it); reps_out: a [sum F, 384] view (any row stride) that receives reps instead of a new tensor."""
+        overwrites it); reps_out: a [sum F, 384] view (any row stride) that receives reps instead of a new tensor.
+        seg (inference, patch 16, streaming, end="blocks"): the pass's SegPlan (_seg_plan): every FRAME of every item is a segment
+        of the stacked rows and the embedding and the attention are one launch each over all segments
+        (csrc/attn_seg.hip): the launch list does not depend on the number of frames or shapes."""
         f = self.flat
         imgs = list(img) if isinstance(img, (list, tuple)) else [img]
         dev = imgs[0].device
@@ -455,7 +521,9 @@ class VisionTransformer(nn.Module):
             raise ValueError("get_last_selfattention takes one resolution")
         # Every decision of the pass, taken once; inside the loop only "is this the last block" is left.
         pl = SimpleNamespace(groups=groups, M=M, NP=NP, Ftot=Ftot, dev=dev, save=save, e16=_empty(torch.bfloat16, dev),
-                             e32=_empty(torch.float32, dev), streaming=streaming, reps_out=reps_out)
+                             e32=_empty(torch.float32, dev), streaming=streaming, reps_out=reps_out, seg=seg)
+        if seg is not None and (save or end != "blocks" or not streaming or self.patch != 16 or seg.M != M):
+            raise NotImplementedError("the segmented pass is the patch-16 streaming inference pass up to the last block")
         # Large M (training step, big extraction batches): the N = 384 GEMMs run on the row-owning kernel with the
         # FOLLOWING LayerNorm in their epilogue (sais_gemm_ln_fwd): proj -> norm2, fc2 -> the next block's norm1.
         # Only block 0's norm1 and the final norm remain stand-alone launches.
@@ -540,6 +608,8 @@ class VisionTransformer(nn.Module):
         """Patchify, patch GEMM (+ bias + positional table) and CLS rows per group -> (patches bf16 [NP, 768], x f32 [M, 384]);
         a patch-8 model (streaming only): the 8 x 8 gather and K = 192."""
         f, K = self.flat, self.patch_k
+        if pl.seg is not None:
+            return self._embed_fwd_seg(pl, imgs)
         gather = ops.patchify_rect8 if self.patch == 8 else ops.patchify_rect if pl.streaming else ops.patchify
         patches = pl.e16(pl.NP, K)
         x = pl.e32(pl.M, D)
@@ -552,6 +622,19 @@ class VisionTransformer(nn.Module):
             ops.gemm_nt(pg, f.w("patch_embed.proj.weight").view(D, K), L.EPI_PATCH_F32, xg,
                         bias=f.w32("patch_embed.proj.bias"), aux=pos, grp=(ntok - 1, ntok, 1))
             ops.vit_cls_rows(f.w32("cls_token"), pos, xg, Fr, ntok)
+        return patches, x
+
+    def _embed_fwd_seg(self, pl, imgs):
+        """_embed_fwd of a segmented pass, four launches whatever the frames: the pixels packed, one gather, the patch GEMM with
+        its bias over all patch rows, and the token rows (CLS rows, patch rows + the positional table interpolated per segment
+        from two per-axis tap matrices: no [hw, 196] map per shape)."""
+        f, seg = self.flat, pl.seg
+        pixels = imgs[0].reshape(-1) if len(imgs) == 1 else torch.cat([im.reshape(-1) for im in imgs])
+        patches, pe, x = pl.e16(pl.NP, PATCH_K), pl.e32(pl.NP, D), pl.e32(pl.M, D)
+        ops.patchify_seg(pixels, seg, patches)
+        ops.gemm_nt(patches, f.w("patch_embed.proj.weight").view(D, PATCH_K), L.EPI_BIAS_F32, pe,
+                    bias=f.w32("patch_embed.proj.bias"))
+        ops.vit_embed_seg(pe, f.w32("cls_token"), f.w32("pos_embed"), seg, x)
         return patches, x
 
     def _droppath_draw(self, groups, dev):
@@ -585,6 +668,9 @@ class VisionTransformer(nn.Module):
         its probabilities f32 [frames, heads, ntok, ntok], which are returned (one group)."""
         f, p, probs = self.flat, f"blocks.{i}.", None
         ops.gemm_nt(b["xn1"], f.w(p + "attn.qkv.weight"), L.EPI_BIAS_BF16, b["qkv"], bias=f.w32(p + "attn.qkv.bias"))
+        if pl.seg is not None:                           # every frame of the pass in one launch
+            ops.vit_attn_fwd_seg(b["qkv"], pl.seg, b["ao"])
+            return None
         for g, lg in zip(pl.groups, b["lse"]):
             if want_probs:
                 probs = pl.e32(g["Fr"], HEADS, g["ntok"], g["ntok"])
