@@ -1087,7 +1087,7 @@ int sais_center_rows(float* x, long ldx, long rows, int dim, const float* mean, 
 int sais_rank_positions(const float* sim, long ld, int Nq, int Ndb, const int* offsets, const int* items, int* pos, void* stream);
 int sais_resize_bilinear_f32(const float* x, int frames, int H, int W, double scale, float* y, int Ho, int Wo, void* stream);
 
-/* ================================================================ frames of different sizes in one backbone pass (inference)
+/* ================================================================ frames of different sizes in one backbone pass
  * (sais_amd/csrc/attn_seg.hip, host: sais_amd/vit_seg.py and VisionTransformer.retrieval_features / dense_features on a list).
  * Additive entries: the ABI version does not change.  Patch 16 only.  No atomics: every entry is bit-reproducible.
  * A pass is described by one table with one sais_vit_seg record per FRAME (a segment of the stacked [M, .] token rows):
@@ -1135,6 +1135,44 @@ int sais_vit_embed_seg(const float* patch_out, const float* cls, const float* po
                        const sais_vit_seg* segs_host, const sais_vit_seg* segs_dev, int nseg, float* x, long rows, void* stream);
 int sais_vit_cls_gather_seg(const float* x, long ldx, long rows, const sais_vit_seg* segs_host, const sais_vit_seg* segs_dev,
                             int nseg, float* out, void* stream);
+
+/* ---------------------------------------------------------------- the backward of the segmented pass (training on mixed sizes)
+ * Additive entries in the same file; the table rules above hold, no entry uses atomics, two calls are bit-equal.
+ * sais_vit_attn_bwd_seg: the backward of sais_vit_attn_fwd_seg over all segments in TWO launches, as sais_vit_attn_bwd_any: the
+ *   forward's tile table read as (segment, first query) for delta and dQ, then as (segment, first key) for dK and dV; the rows per
+ *   workgroup are sais_vit_seg_qtile(...) in both.  qkv / dqkv bf16 [rows, 1152], dout / out bf16 [rows, 384] (row strides
+ *   multiples of 8, >= 1152 / 384), lse f32 [6 * rows] as the segmented forward wrote it ([6, ntok] at 6 row0), workspace: the f32
+ *   delta in the same layout, sais_vit_attn_bwd_seg_workspace_bytes(rows) = 24 rows bytes (0 for rows <= 0).  Every element of dqkv
+ *   inside a segment has exactly one writer; rows (and pad columns) outside every segment are never touched.
+ *   Contract: the bytes of dqkv written for segment s equal what sais_vit_attn_bwd_any(frames = 1, ntok) writes for
+ *   (qkv + row0 ldqkv, dout + row0 lddo, out + row0 ldout, lse + 6 row0, dqkv + row0 lddqkv), in either workgroup form and with
+ *   padded row strides: both files run the two tile bodies of csrc/attn_stream_bwd.hpp.
+ *   SAIS_ERR_ARG and nothing launched: what sais_vit_attn_fwd_seg refuses, a null lse / dout / dqkv / workspace, a short workspace.
+ * sais_vit_embed_bwd_seg (dense): the backward of sais_vit_embed_seg from dx f32 [rows, 384] (contiguous), accumulated INTO the
+ *   gradient buffers as sais_vit_embed_bwd does:
+ *     dpatch bf16 [sum gh gw, 384] = bf16(dx) of the patch rows in segment order (the dY operand of sais_gemm_tn);
+ *     dcls[384] += sum_s dx[row0_s];  dpos[0] += the same sum;
+ *     dpos[1 + 14 a + b] += sum_s sum_y sum_x Ty_s[y][a] Tx_s[x][b] dx[row0_s + 1 + y gw + x]   (a 14 x 14 segment: its rows).
+ *   f32, fixed order: one workgroup owns one row of dpos; it cuts the segments into 8 runs of ceil(nseg / 8) consecutive ones,
+ *   sums each run from 0 in ascending (segment, y, x) over the non-zero taps as acc = fma(Ty Tx, dx, acc) (the product rounded to
+ *   f32 first; weight one for a 14 x 14 segment), adds the 8 partial sums in ascending order from 0 and adds the total to the
+ *   buffer.  Per element the error is at most (terms + 2) 2^-24 sum |Ty Tx dx| (+ 2^-24 |the value it is added to|).
+ * sais_vit_cls_scatter_seg: dst[row0 of segment s] = src[s] (src f32 [nseg, 384] contiguous; dst f32, row stride ldd >= 384, a
+ *   multiple of 4; the other rows are not touched): the inverse of sais_vit_cls_gather_seg.
+ * sais_vit_rows_expand_seg (dense, rows = the rows of the pass): out f32 [nb, rows], out[b][r] = per_seg[b][segment of r]
+ *   (per_seg f32 [nb, nseg]): per-segment DropPath scales (sais_droppath_scales with samples = nseg, rows_per_sample = 1) as the
+ *   per-row scales the GEMM epilogues read.                                                                                    */
+size_t sais_vit_attn_bwd_seg_workspace_bytes(long rows);
+int sais_vit_attn_bwd_seg(const void* qkv, long ldqkv, const void* dout, long lddo, const void* out, long ldout, const float* lse,
+                          long rows, const sais_vit_seg* segs_host, const sais_vit_seg* segs_dev, int nseg, const int* tiles_host,
+                          const int* tiles_dev, int ntiles, void* dqkv, long lddqkv, void* workspace, size_t workspace_bytes,
+                          void* stream);
+int sais_vit_embed_bwd_seg(const float* dx, long rows, const float* taps_dev, long ntaps, const sais_vit_seg* segs_host,
+                           const sais_vit_seg* segs_dev, int nseg, float* dcls, float* dpos, void* dpatch_bf16, void* stream);
+int sais_vit_cls_scatter_seg(const float* src, const sais_vit_seg* segs_host, const sais_vit_seg* segs_dev, int nseg, float* dst,
+                             long ldd, long rows, void* stream);
+int sais_vit_rows_expand_seg(const float* per_seg, int nb, const sais_vit_seg* segs_host, const sais_vit_seg* segs_dev, int nseg,
+                             float* out, long rows, void* stream);
 
 #ifdef __cplusplus
 }

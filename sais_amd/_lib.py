@@ -333,6 +333,13 @@ SIGNATURES = {
     "sais_patchify_seg": [c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
     "sais_vit_embed_seg": [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p, c_long, c_void_p],
     "sais_vit_cls_gather_seg": [c_void_p, c_long, c_long, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
+    # ... and its backward
+    "sais_vit_attn_bwd_seg_workspace_bytes": [c_long],
+    "sais_vit_attn_bwd_seg": [c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_int,
+                              c_void_p, c_void_p, c_int, c_void_p, c_long, c_void_p, ctypes.c_size_t, c_void_p],
+    "sais_vit_embed_bwd_seg": [c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "sais_vit_cls_scatter_seg": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_long, c_long, c_void_p],
+    "sais_vit_rows_expand_seg": [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_long, c_void_p],
 }
 
 _lib = None
@@ -369,6 +376,7 @@ def load():
     lib.sais_knn_workspace_bytes.restype = ctypes.c_size_t
     lib.sais_colmean_cov_workspace_bytes.restype = ctypes.c_size_t
     lib.sais_vit_attn_bwd_any_workspace_bytes.restype = ctypes.c_size_t
+    lib.sais_vit_attn_bwd_seg_workspace_bytes.restype = ctypes.c_size_t
     lib.sais_last_error.restype = ctypes.c_char_p
     lib.sais_last_error.argtypes = []
     _lib = lib

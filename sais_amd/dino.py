@@ -17,6 +17,7 @@ torch.cuda.amp fp16 autocast + GradScaler (`--use_fp16`; no loss scaling is need
 crops it returns, `[2 x [B,3,224,224]] + [n_local x [B,3,96,96]]`.
 """
 import math
+import os
 
 import numpy as np
 import torch
@@ -178,7 +179,11 @@ class DINOHead(nn.Module):
 
 # --------------------------------------------------------------------------- MultiCropWrapper
 class MultiCropWrapper(nn.Module):
-    """utils.py:595-630: one backbone pass per run of equal-resolution crops, one head pass over all features."""
+    """utils.py:595-630: one backbone pass per run of equal-resolution crops, one head pass over all features.
+    `segmented` (default False; True when the environment has SAIS_DINO_SEGMENTED=1): every crop goes through the backbone as
+    segments of ONE segmented pass (VisionTransformer.forward on a list) instead of resolution groups, at any crop sizes,
+    224 / 96 included: the launch list then does not depend on the number of crop sizes.  Off by default: at 224 / 96 the
+    resident attention of the group pass is faster (LABNOTES R35.1)."""
 
     def __init__(self, backbone, head):
         super().__init__()
@@ -187,6 +192,7 @@ class MultiCropWrapper(nn.Module):
         backbone.fc, backbone.head = nn.Identity(), nn.Identity()
         self.backbone = backbone
         self.head = head
+        self.segmented = os.environ.get("SAIS_DINO_SEGMENTED", "0") == "1"
 
     @staticmethod
     def _groups(x):
@@ -208,6 +214,12 @@ class MultiCropWrapper(nn.Module):
         """All resolution groups go through the backbone in ONE pass (rows stacked: sais_amd.vit._forward_kernels), the
         features come back in crop order, exactly the concatenation utils.py:626 builds."""
         bb = self.backbone
+        if self.segmented:                          # every crop a run of segments: one launch list whatever the crop sizes
+            items = bb._check_list(x if isinstance(x, (list, tuple)) else [x], "forward")
+            bb._engine(items[0].device)
+            feat, bsaved = bb._forward_kernels(items, save=save, streaming=True, seg=bb._seg_plan(items))
+            logits, hsaved = self.head.forward_kernels(feat, save)
+            return logits, (bsaved, hsaved) if save else None
         # patch 16: crops of any H x W in multiples of 16; a pass with a group off 224 x 224 / 96 x 96 is a streaming one
         any_size = "forward" if bb.patch == 16 else None
         groups = [bb._check_input(g, any_size) for g in self._groups(x)]
@@ -539,6 +551,12 @@ class GraphedTrainStep:
         self.student, self.teacher, self.dino_loss, self.optimizer = student, teacher, dino_loss, optimizer
         self.images, self.clip_grad, self.want_norms = list(images), clip_grad, want_norms
         self._graph, self._temp, self._out = None, None, None
+        self._refuse_segmented()
+
+    def _refuse_segmented(self):
+        if getattr(self.student, "segmented", False):
+            raise NotImplementedError("GraphedTrainStep does not capture a segmented student (MultiCropWrapper.segmented): its "
+                                      "pass builds a host table per call, so run dino.train_step eagerly or set segmented = False")
 
     def step_state(self):
         """Snapshot of EVERYTHING the captured part of a step mutates besides the gradients (rebuilt every step): the DINO
@@ -564,6 +582,7 @@ class GraphedTrainStep:
             sync.bytes, sync.log, sync.last_buckets = st["sync_counters"][0], list(st["sync_counters"][1]), list(st["sync_counters"][2])
 
     def _capture(self, epoch):
+        self._refuse_segmented()
         fn = lambda: _forward_backward(self.student, self.teacher, self.dino_loss, self.optimizer, self.images, epoch,
                                        self.clip_grad, self.want_norms)
         side = torch.cuda.Stream()

@@ -414,6 +414,52 @@ def vit_cls_gather_seg(x, plan, out):
     L.call("sais_vit_cls_gather_seg", _p(x), x.stride(0), x.shape[0], plan.segs_host, plan.segs_dev, plan.nseg, _p(out), _stream())
 
 
+def vit_attn_bwd_seg(qkv, dout, out, lse, plan, dqkv):
+    """The streaming attention backward over every segment of a mixed-size pass in two launches (csrc/attn_seg.hip): out and lse
+    f32 [6 * rows] are what vit_attn_fwd_seg wrote.  The delta workspace is the one vit_attn_bwd_any's calls share."""
+    _chk(qkv, BF16, "qkv"); _chk(dout, BF16, "dout"); _chk(out, BF16, "out"); _chk(lse, F32, "lse"); _chk(dqkv, BF16, "dqkv")
+    rows = min(qkv.shape[0], dout.shape[0], out.shape[0], dqkv.shape[0])
+    if lse.numel() < 6 * rows:
+        raise L.SaisHipError("lse: expected 6 floats per stacked row")
+    ws = _attn_any_ws(int(L.load().sais_vit_attn_bwd_seg_workspace_bytes(rows)), qkv.device)
+    sq = sum(n * n for n in plan.ntoks)
+    _timed("vit_attn_bwd_seg", 14.0 * 6 * sq * 64, 2 * plan.M * 384 * 9,
+           lambda: L.call("sais_vit_attn_bwd_seg", _p(qkv), qkv.stride(0), _p(dout), dout.stride(0), _p(out), out.stride(0),
+                          _p(lse), rows, plan.segs_host, plan.segs_dev, plan.nseg, plan.tiles_host, plan.tiles_dev, plan.ntiles,
+                          _p(dqkv), dqkv.stride(0), _p(ws), ws.numel(), _stream()))
+
+
+def vit_embed_bwd_seg(dx, plan, dcls, dpos, dpatch):
+    """The backward of vit_embed_seg from dx f32 [plan.M, 384]: dpatch bf16 [plan.NP, 384] written, dcls f32 [384] and dpos f32
+    [197, 384] accumulated into (csrc/attn_seg.hip: f32, fixed order, no atomics)."""
+    _chk(dx, F32, "dx"); _chk(dcls, F32, "dcls"); _chk(dpos, F32, "dpos"); _chk(dpatch, BF16, "dpatch")
+    if not (dx.is_contiguous() and dpatch.is_contiguous() and dpos.is_contiguous()) or dx.shape[0] < plan.M or \
+            dpatch.numel() < plan.NP * 384 or dpos.numel() < 197 * 384 or dcls.numel() < 384:
+        raise L.SaisHipError("vit_embed_bwd_seg: expected contiguous dx [M, 384], dpatch [NP, 384], dpos [197, 384], dcls [384]")
+    L.call("sais_vit_embed_bwd_seg", _p(dx), dx.shape[0], plan.taps_dev, plan.ntaps, plan.segs_host, plan.segs_dev, plan.nseg,
+           _p(dcls), _p(dpos), _p(dpatch), _stream())
+
+
+def vit_cls_scatter_seg(src, plan, dst):
+    """dst[row0 of every segment] = src f32 [plan.nseg, 384]; the other rows of dst f32 [rows, 384] are left as they are."""
+    _chk(src, F32, "src"); _chk(dst, F32, "dst")
+    if not src.is_contiguous() or src.numel() < plan.nseg * 384:
+        raise L.SaisHipError(f"src: expected a contiguous [{plan.nseg}, 384] tensor")
+    L.call("sais_vit_cls_scatter_seg", _p(src), plan.segs_host, plan.segs_dev, plan.nseg, _p(dst), dst.stride(0), dst.shape[0],
+           _stream())
+
+
+def vit_rows_expand_seg(per_seg, plan):
+    """f32 [nb, plan.nseg] (one value per segment) -> f32 [nb, plan.M] (the value of a row's segment)."""
+    _chk(per_seg, F32, "per_seg")
+    if per_seg.dim() != 2 or not per_seg.is_contiguous() or per_seg.shape[1] != plan.nseg:
+        raise L.SaisHipError(f"per_seg: expected a contiguous [nb, {plan.nseg}] tensor")
+    out = torch.empty(per_seg.shape[0], plan.M, dtype=F32, device=per_seg.device)
+    L.call("sais_vit_rows_expand_seg", _p(per_seg), per_seg.shape[0], plan.segs_host, plan.segs_dev, plan.nseg, _p(out), plan.M,
+           _stream())
+    return out
+
+
 def vit_cls_probs(q, k, frames, ntok, probs):
     """Row 0 of the last block's softmax (csrc/attnviz.hip): q bf16 [frames, 384] (the CLS queries), k bf16 [frames*ntok, 384]
     (row stride free: the K third of a qkv buffer in place) -> probs f32 [frames, 6, ntok] over all ntok keys."""
@@ -452,7 +498,10 @@ _ATTN_ANY_WS = {}
 def vit_attn_bwd_any_workspace(frames, ntok, device):
     """The delta workspace of vit_attn_bwd_any, one per (device, bytes): launches on a stream are ordered, so consecutive calls
     share it.  While the stream is capturing: a fresh buffer from the graph's pool."""
-    n = int(L.load().sais_vit_attn_bwd_any_workspace_bytes(frames, ntok))
+    return _attn_any_ws(int(L.load().sais_vit_attn_bwd_any_workspace_bytes(frames, ntok)), device)
+
+
+def _attn_any_ws(n, device):
     if torch.cuda.is_current_stream_capturing():
         return torch.empty(n, dtype=torch.uint8, device=device)
     key = (str(device), n)

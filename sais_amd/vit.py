@@ -23,6 +23,10 @@ csrc/attn_any.hip), and forward() whenever it needs gradients (training at any f
 every resolution group is 224 x 224 or 96 x 96 keeps the resident kernels and the launches it always had), and
 `cls_attention` ends in the CLS row of the last block's softmax (csrc/attnviz.hip) instead of `get_last_selfattention`'s
 [F, 6, N, N] tensor, which stays a 224 x 224 / 96 x 96 call.
+Frames of DIFFERENT sizes go through one pass as segments of the stacked token rows (csrc/attn_seg.hip, vit_seg.SegPlan): a list
+of tensors given to `dense_features`, `retrieval_features(cls_only=True)` (inference) or `forward` (under grad: a training pass,
+whose backward runs sais_vit_attn_bwd_seg and sais_vit_embed_bwd_seg; without: the retrieval call's bits); the launch list does
+not depend on the number of frames or shapes.  Patch 16 only.
 `vit_small(patch_size=8)` (ViT-S/8: 8 x 8 patches, a 28 x 28 positional grid, 785 tokens at 224 x 224) is an INFERENCE backbone: every
 method takes any H x W in multiples of 8 up to 4097 tokens and runs the streaming launch list with the 8 x 8 gather (csrc/vit8.hip)
 and the patch GEMM at K = 192; forward() and probe_features() keep the CLS-only last block, whose attention beyond the 200 tokens of
@@ -168,17 +172,17 @@ class _ViTFn(torch.autograd.Function):
     kernels into model.flat.grad (p.grad views) as a side effect; `anchor` only keeps the node alive."""
 
     @staticmethod
-    def forward(ctx, model, x, anchor, streaming=False):
-        reps, saved = model._forward_kernels(x, save=True, streaming=streaming)
+    def forward(ctx, model, x, anchor, streaming=False, seg=None):
+        reps, saved = model._forward_kernels(x, save=True, streaming=streaming, seg=seg)     # seg: x is a list, one segmented pass
         ctx.model, ctx.saved = model, saved
-        ctx.x_requires_grad = x.requires_grad
+        ctx.x_requires_grad = seg is None and x.requires_grad
         return reps
 
     @staticmethod
     def backward(ctx, dreps):
         ctx.model._backward_kernels(ctx.saved, dreps.contiguous())
         ctx.saved = None
-        return None, None, None, None
+        return None, None, None, None, None
 
 
 class VisionTransformer(nn.Module):
@@ -206,6 +210,7 @@ class VisionTransformer(nn.Module):
         self._bp, self._wsbuf = None, {}
         self._rng = None
         self.last_droppath_scales = None
+        self.last_droppath_frame_scales = None       # a segmented pass: one column per frame, f32 [2 x depth, nseg]
         self.patch_embed = _PatchEmbed(patch_size)
         self.cls_token = nn.Parameter(torch.zeros(1, 1, D))
         self.pos_embed = nn.Parameter(torch.zeros(1, self.ntok0, D))
@@ -254,7 +259,19 @@ class VisionTransformer(nn.Module):
 
     # ------------------------------------------------------------------ public API (reference signatures)
     def forward(self, x):
+        """norm(x)[:, 0] (:209-214), f32 [F, 384].  x a LIST or tuple of tensors [F_i, 3, H_i, W_i] of different sizes (patch 16;
+        the checks and error texts of dense_features on a list): f32 [sum F_i, 384] in list order from ONE segmented pass over
+        all frames, whose launch list does not depend on the number of frames or shapes.  Under grad it is a training pass
+        (_forward_kernels with `seg` and `save`, every row of the last block computed; the backward is
+        sais_vit_attn_bwd_seg / sais_vit_embed_bwd_seg, csrc/attn_seg.hip); without, the bits of
+        retrieval_features(list, cls_only=True)."""
         need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in (self.cls_token, self.norm.weight))
+        if isinstance(x, (list, tuple)):
+            items = self._check_list(x, "forward")
+            if not need_grad:
+                return self.retrieval_features(items, cls_only=True)
+            self._engine(items[0].device)
+            return _ViTFn.apply(self, items, self._anchor, True, self._seg_plan(items))
         if self.patch == 8:
             if need_grad:
                 raise NotImplementedError("the patch-8 backbone is inference only (call it under torch.no_grad() or freeze its "
@@ -510,9 +527,13 @@ class VisionTransformer(nn.Module):
         pass has no block-level C call and no fused-MLP kernel, in either direction.  tap(i, x): called
         after every block but a CLS-only last one with the residual stream the block left (without `save` the next block
         overwrites it); reps_out: a [sum F, 384] view (any row stride) that receives reps instead of a new tensor.
-        seg (inference, patch 16, streaming, end="blocks"): the pass's SegPlan (_seg_plan): every FRAME of every item is a segment
+        seg (patch 16, streaming, end="blocks" or "reps"): the pass's SegPlan (_seg_plan): every FRAME of every item is a segment
         of the stacked rows and the embedding and the attention are one launch each over all segments
-        (csrc/attn_seg.hip): the launch list does not depend on the number of frames or shapes."""
+        (csrc/attn_seg.hip): the launch list does not depend on the number of frames or shapes.  end="reps": the CLS rows
+        gathered (sais_vit_cls_gather_seg) for one final-norm launch; the last block runs on every row (the one-wave CLS
+        kernels take one token count per launch).  With `save` the attention keeps its log-sum-exp ([6, ntok] at 6 row0 of one
+        f32 [6 M] tensor per block), DropPath is drawn per segment in list order, and `saved` records the plan: the backward
+        follows it (sais_vit_attn_bwd_seg, sais_vit_embed_bwd_seg: no per-shape launch in either direction)."""
         f = self.flat
         imgs = list(img) if isinstance(img, (list, tuple)) else [img]
         dev = imgs[0].device
@@ -522,8 +543,8 @@ class VisionTransformer(nn.Module):
         # Every decision of the pass, taken once; inside the loop only "is this the last block" is left.
         pl = SimpleNamespace(groups=groups, M=M, NP=NP, Ftot=Ftot, dev=dev, save=save, e16=_empty(torch.bfloat16, dev),
                              e32=_empty(torch.float32, dev), streaming=streaming, reps_out=reps_out, seg=seg)
-        if seg is not None and (save or end != "blocks" or not streaming or self.patch != 16 or seg.M != M):
-            raise NotImplementedError("the segmented pass is the patch-16 streaming inference pass up to the last block")
+        if seg is not None and (end not in ("blocks", "reps") or not streaming or self.patch != 16 or seg.M != M):
+            raise NotImplementedError("the segmented pass is the patch-16 streaming pass to the last block or the final norm")
         # Large M (training step, big extraction batches): the N = 384 GEMMs run on the row-owning kernel with the
         # FOLLOWING LayerNorm in their epilogue (sais_gemm_ln_fwd): proj -> norm2, fc2 -> the next block's norm1.
         # Only block 0's norm1 and the final norm remain stand-alone launches.
@@ -533,7 +554,7 @@ class VisionTransformer(nn.Module):
         # recorded in `saved`, the backward follows it)
         # and a pass that is saved for a backward keeps the CLS-only tail only while sais_vit_attn_cls_bwd holds every group (one wave
         # per (frame, head): CLS_WAVE_MAX_TOKENS); past it the last block is computed on every row
-        pl.prune = end == "reps" and self.prune_last_block and Ftot < ops.ROW_GEMM_MIN_M and \
+        pl.prune = end == "reps" and self.prune_last_block and Ftot < ops.ROW_GEMM_MIN_M and seg is None and \
             not (save and any(g["ntok"] > CLS_WAVE_MAX_TOKENS for g in groups))
         pl.prune_q = pl.prune and len(groups) == 1 and _PRUNE_Q
         pl.mlp_fused = not streaming and ops.mlp_fused_enabled(M)      # (the streaming pass has never taken that switch)
@@ -544,9 +565,9 @@ class VisionTransformer(nn.Module):
             and not streaming
         patches, x = self._embed_fwd(pl, imgs)
         draw = self.training and self.drop_path_rate > 0 and end != "probs"
-        pl.dp = dp = self._droppath_draw(groups, dev) if draw else None
+        pl.dp = dp = (self._droppath_draw(groups, dev) if seg is None else self._droppath_draw_seg(seg, dev)) if draw else None
         saved = {"patches": patches, "blocks": [], "groups": groups, "M": M, "Ftot": Ftot, "dp": dp, "streaming": streaming,
-                 "pruned": False} if save else None
+                 "pruned": False, "seg": seg} if save else None
         b = ln1 = None                                   # the block's tensors; (xn, mean1, rstd1) of its norm1
         # norm1's outputs for a block: its own with `save`, else one xn for the whole pass and no statistics
         norm1_out = lambda: (pl.e16(M, D), pl.e32(M), pl.e32(M)) if save else ln1 or (pl.e16(M, D), None, None)
@@ -599,9 +620,9 @@ class VisionTransformer(nn.Module):
                 tap(i, x)
         if end == "blocks":
             return x, saved
-        reps, meanN, rstdN = self._final_norm_fwd(pl, x)
+        reps, meanN, rstdN, x_final = self._final_norm_fwd(pl, x)      # x_final: what the norm read (the gathered CLS rows or x)
         if save:
-            saved.update(x_final=x, meanN=meanN, rstdN=rstdN)
+            saved.update(x_final=x_final, meanN=meanN, rstdN=rstdN)
         return reps, saved
 
     def _embed_fwd(self, pl, imgs):
@@ -637,13 +658,17 @@ class VisionTransformer(nn.Module):
         ops.vit_embed_seg(pe, f.w32("cls_token"), f.w32("pos_embed"), seg, x)
         return patches, x
 
-    def _droppath_draw(self, groups, dev):
-        """DropPath (train mode): row scales keep_f / (1 - p_i) for the 2 x depth residual branches, one Philox draw per
-        frame and branch; branch 2i = attention of block i, 2i + 1 = its MLP.  f32 [2 x depth, M]."""
+    def _droppath_state(self, dev):
+        """The Philox state and the per-branch rates on the device, made on first use."""
         if self._rng is None or self._rng.device != dev:
             self._rng = ops.rng_state(self.drop_path_seed, dev)
             rates = torch.linspace(0, self.drop_path_rate, self.depth).repeat_interleave(2)      # :150
             self._dp_rates = rates.to(dev, torch.float32)
+
+    def _droppath_draw(self, groups, dev):
+        """DropPath (train mode): row scales keep_f / (1 - p_i) for the 2 x depth residual branches, one Philox draw per
+        frame and branch; branch 2i = attention of block i, 2i + 1 = its MLP.  f32 [2 x depth, M]."""
+        self._droppath_state(dev)
         parts = []
         for g in groups:                                 # one advance + draw per group (what separate passes would do)
             ops.rng_advance(self._rng)
@@ -652,13 +677,23 @@ class VisionTransformer(nn.Module):
         self.last_droppath_scales = dp
         return dp
 
+    def _droppath_draw_seg(self, seg, dev):
+        """_droppath_draw of a segmented pass: ONE advance and one launch that draws per segment in list order
+        (`last_droppath_frame_scales`, f32 [2 x depth, nseg]), expanded to the rows by one more (f32 [2 x depth, M])."""
+        self._droppath_state(dev)
+        ops.rng_advance(self._rng)
+        per = self.last_droppath_frame_scales = ops.droppath_scales(self._dp_rates, seg.nseg, 1, self._rng)
+        dp = self.last_droppath_scales = ops.vit_rows_expand_seg(per, seg)
+        return dp
+
     @staticmethod
     def _block_buffers(pl, x, ln1):
         """The tensors of one block, for the C call or the launch list; with `save` this dict is what the backward gets.  Without,
         the stream is updated in place and only the launch list needs h (the C call keeps GELU(u) in its workspace)."""
         M, save, e16, e32 = pl.M, pl.save, pl.e16, pl.e32
         return dict(x_in=x, mean1=ln1[1], rstd1=ln1[2], xn1=ln1[0], qkv=e16(M, 3 * D), ao=e16(M, D),
-                    lse=[e32(g["Fr"], HEADS, g["ntok"]) if save else None for g in pl.groups],
+                    lse=[e32(HEADS * M) if save else None] if pl.seg is not None else
+                    [e32(g["Fr"], HEADS, g["ntok"]) if save else None for g in pl.groups],
                     x_mid=e32(M, D) if save else x, mean2=e32(M) if save else None, rstd2=e32(M) if save else None,
                     xn2=e16(M, D), dgelu=ops.gelu_grad_buffer(M, HID, pl.dev) if save else None,
                     h=e16(M, HID) if save or not pl.block_call else None)
@@ -669,7 +704,7 @@ class VisionTransformer(nn.Module):
         f, p, probs = self.flat, f"blocks.{i}.", None
         ops.gemm_nt(b["xn1"], f.w(p + "attn.qkv.weight"), L.EPI_BIAS_BF16, b["qkv"], bias=f.w32(p + "attn.qkv.bias"))
         if pl.seg is not None:                           # every frame of the pass in one launch
-            ops.vit_attn_fwd_seg(b["qkv"], pl.seg, b["ao"])
+            ops.vit_attn_fwd_seg(b["qkv"], pl.seg, b["ao"], b["lse"][0])
             return None
         for g, lg in zip(pl.groups, b["lse"]):
             if want_probs:
@@ -714,16 +749,23 @@ class VisionTransformer(nn.Module):
                             aux=x_mid, rowscale=rs_mlp)
 
     def _final_norm_fwd(self, pl, x):
-        """The final norm on the CLS rows only (row stride = ntok * 384).  Returns (reps f32 [frames, 384], mean, rstd)."""
+        """The final norm on the CLS rows only (row stride = ntok * 384; a segmented pass gathers them first).  Returns
+        (reps f32 [frames, 384], mean, rstd, the tensor the norm read)."""
         f, Ftot = self.flat, pl.Ftot
         reps = pl.e32(Ftot, D) if pl.reps_out is None else pl.reps_out
         meanN, rstdN = (pl.e32(Ftot), pl.e32(Ftot)) if pl.save else (None, None)
+        if pl.seg is not None:                           # the CLS rows gathered, then the launch of retrieval_features(list)
+            cls = pl.e32(Ftot, D)
+            ops.vit_cls_gather_seg(x, pl.seg, cls)
+            ops.layernorm_fwd(cls, Ftot, D, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6, y32=reps, mean=meanN, rstd=rstdN,
+                              ldy32=reps.stride(0))
+            return reps, meanN, rstdN, cls
         for g in pl.groups:
             fr = g["frames"]
             ops.layernorm_fwd(x[g["rows"]], g["Fr"], g["ntok"] * D, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6,
                               y32=reps[fr], mean=None if meanN is None else meanN[fr],
                               rstd=None if rstdN is None else rstdN[fr], ldy32=reps.stride(0))
-        return reps, meanN, rstdN
+        return reps, meanN, rstdN, x
 
     def _block_params(self, i):
         """ctypes parameter blocks of the Blocks (pointers into the flat buffers), rebuilt when those are."""
@@ -861,7 +903,8 @@ class VisionTransformer(nn.Module):
         hooked = self.grad_ready_hook is not None and getattr(self.grad_ready_hook, "active", True)
         # blocks per weight-gradient launch (_PendingDW); 1: every block launches its own
         G = ops.dw_group(dp_hooks=hooked) if fused and M % 32 == 0 and not mlp_fused else 1
-        pl = SimpleNamespace(groups=groups, M=M, e16=e16, fused=fused, mlp_fused=mlp_fused, defer=G > 1, streaming=streaming)
+        pl = SimpleNamespace(groups=groups, M=M, e16=e16, fused=fused, mlp_fused=mlp_fused, defer=G > 1, streaming=streaming,
+                             seg=saved.get("seg"))
         pend = _PendingDW(self, saved, G, hooked)
         dxa = e16(M, D)                            # bf16 copy of the residual-stream gradient that enters a block
         # scratch of the launch list (the C call has its workspace; dqkv also serves the CLS-only block): dxb = the bf16 gradient at
@@ -899,9 +942,15 @@ class VisionTransformer(nn.Module):
         self._embed_bwd(saved, dx)
 
     def _final_norm_bwd(self, saved, dreps, dx, dxa):
-        """Backward of the final norm on the CLS rows into the (zeroed) residual-stream gradient, and its bf16 copy."""
-        f = self.flat
-        for g in saved["groups"]:
+        """Backward of the final norm on the CLS rows into the (zeroed) residual-stream gradient, and its bf16 copy.  A
+        segmented pass: on the gathered [nseg, 384] rows, then scattered to the CLS rows (sais_vit_cls_scatter_seg)."""
+        f, seg = self.flat, saved.get("seg")
+        if seg is not None:
+            dcls = torch.empty(seg.nseg, D, dtype=torch.float32, device=dx.device)
+            ops.layernorm_bwd(saved["x_final"], D, saved["meanN"], saved["rstdN"], f.w32("norm.weight"), seg.nseg, dy32=dreps,
+                              dx32=dcls, dgamma=f.g("norm.weight"), dbeta=f.g("norm.bias"))
+            ops.vit_cls_scatter_seg(dcls, seg, dx)
+        for g in saved["groups"] if seg is None else ():
             r, fr = g["rows"], g["frames"]
             ops.layernorm_bwd(saved["x_final"][r], g["ntok"] * D, saved["meanN"][fr], saved["rstdN"][fr], f.w32("norm.weight"),
                               g["Fr"], dy32=dreps[fr], dx32=dx[r], lddx32=g["ntok"] * D, dgamma=f.g("norm.weight"),
@@ -940,7 +989,9 @@ class VisionTransformer(nn.Module):
                               rowscale16=rs_attn)
         # attention branch
         ops.gemm_nt(dxb, f.wt16[p + "attn.proj.weight"], L.EPI_BIAS_BF16, dao)
-        for g, lg in zip(pl.groups, s["lse"]):
+        if pl.seg is not None:                        # every frame of the pass in two launches
+            ops.vit_attn_bwd_seg(s["qkv"], dao, s["ao"], s["lse"][0], pl.seg, dqkv)
+        for g, lg in zip(pl.groups, s["lse"]) if pl.seg is None else ():
             r = g["rows"]
             if pl.streaming:
                 ops.vit_attn_bwd_any(s["qkv"][r], dao[r], s["ao"][r], lg, g["Fr"], g["ntok"], dqkv[r])
@@ -967,10 +1018,13 @@ class VisionTransformer(nn.Module):
                               rowscale16=rs_prev)
 
     def _embed_bwd(self, saved, dx):
-        """Backward of the embedding per group, then the patch projection's weight gradient over all groups."""
-        f = self.flat
+        """Backward of the embedding per group (a segmented pass: sais_vit_embed_bwd_seg over all segments), then the patch
+        projection's weight gradient over all rows."""
+        f, seg = self.flat, saved.get("seg")
         dpatch = torch.empty(saved["patches"].shape[0], D, dtype=torch.bfloat16, device=dx.device)
-        for g in saved["groups"]:
+        if seg is not None:                         # one entry over all segments, through the per-axis taps: no [hw, 196] map
+            ops.vit_embed_bwd_seg(dx, seg, f.g("cls_token"), f.g("pos_embed"), dpatch)
+        for g in saved["groups"] if seg is None else ():
             Fr, ntok = g["Fr"], g["ntok"]
             dxg, dpg = dx[g["rows"]], dpatch[g["prows"]]
             if g["interp"] is None:
