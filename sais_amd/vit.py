@@ -1,36 +1,30 @@
-"""DINO ViT-S/16 spatial encoder on MI355X — drop-in for the reference's
-SAIS/scripts/dino-main/vision_transformer.py (`vit_small`, `VisionTransformer.forward` :209-214,
-`get_last_selfattention` :216-223, `get_intermediate_layers` :225-233) with the same parameter names / shapes (150-tensor state_dict,
-SURVEY App. A), so `dino_deitsmall16_pretrain.pth` loads strictly.
+"""DINO ViT-S/16 spatial encoder on MI355X — drop-in for the reference's SAIS/scripts/dino-main/vision_transformer.py
+(`vit_small`, `VisionTransformer.forward` :209-214, `get_last_selfattention` :216-223, `get_intermediate_layers` :225-233) with
+the same parameter names / shapes (150-tensor state_dict), so `dino_deitsmall16_pretrain.pth` loads strictly.
 
 Every block runs as hand-written gfx950 kernels through the C ABI (include/sais_hip.h):
-  LN -> [MFMA GEMM qkv] -> [LDS-resident attention] -> [MFMA GEMM proj + residual] ->
-  LN -> [MFMA GEMM fc1 + GELU] -> [MFMA GEMM fc2 + residual]
-with bf16 MFMA operands, fp32 accumulation, fp32 residual stream and fp32 LN/softmax statistics.
-Backward is hand-written too (dX GEMMs on pre-transposed bf16 weight shadows, dW GEMMs with
-transposed LDS reads, recompute-from-LSE attention backward); parameter gradients are accumulated
-by the kernels directly into the flat gradient buffer that p.grad views.
+  LN -> [MFMA GEMM qkv] -> [attention] -> [MFMA GEMM proj + residual] -> LN -> [MFMA GEMM fc1 + GELU] -> [MFMA GEMM fc2 + residual]
+with bf16 MFMA operands, fp32 accumulation, fp32 residual stream and fp32 LN/softmax statistics.  Backward is hand-written too
+(dX GEMMs on pre-transposed bf16 weight shadows, dW GEMMs with transposed LDS reads, recompute-from-LSE attention backward);
+parameter gradients are accumulated by the kernels directly into the flat gradient buffer that p.grad views.
 
-Deliberate differences from the reference (documented in DESIGN.md): only the ViT-S/16 geometry is supported, at
-224 x 224 (197 tokens: every SAIS path and DINO's global crops) and 96 x 96 (37 tokens: DINO's local crops,
-main_dino.py:658-663, with interpolate_pos_encoding :174-194 as a fixed bicubic map applied by a HIP kernel).  DropPath (stochastic depth, vision_transformer.py:27-46: train() only, per-sample keep with
-rates linspace(0, drop_path_rate, depth); SAIS itself only ever runs the ViT in eval(), extract_representations.py:
-279,340,362) is applied in the epilogues of the residual GEMMs as a per-row scale; the keep draws come from Philox
-(`drop_path_seed`, this library's stream, not torch's): `last_droppath_scales` holds what a forward used.
-Other resolutions (any H x W in multiples of 16 up to 4097 tokens) take the streaming attention, which moves keys and values
-through LDS in tiles instead of keeping a head resident: `dense_features`, `cls_attention` and `retrieval_features` (inference,
-csrc/attn_any.hip), and forward() whenever it needs gradients (training at any frame size: csrc/attn_any_bwd.hip; a pass in which
-every resolution group is 224 x 224 or 96 x 96 keeps the resident kernels and the launches it always had), and
-`cls_attention` ends in the CLS row of the last block's softmax (csrc/attnviz.hip) instead of `get_last_selfattention`'s
-[F, 6, N, N] tensor, which stays a 224 x 224 / 96 x 96 call.
-Frames of DIFFERENT sizes go through one pass as segments of the stacked token rows (csrc/attn_seg.hip, vit_seg.SegPlan): a list
-of tensors given to `dense_features`, `retrieval_features(cls_only=True)` (inference) or `forward` (under grad: a training pass,
-whose backward runs sais_vit_attn_bwd_seg and sais_vit_embed_bwd_seg; without: the retrieval call's bits); the launch list does
-not depend on the number of frames or shapes.  Patch 16 only.
-`vit_small(patch_size=8)` (ViT-S/8: 8 x 8 patches, a 28 x 28 positional grid, 785 tokens at 224 x 224) is an INFERENCE backbone: every
-method takes any H x W in multiples of 8 up to 4097 tokens and runs the streaming launch list with the 8 x 8 gather (csrc/vit8.hip)
-and the patch GEMM at K = 192; forward() and probe_features() keep the CLS-only last block, whose attention beyond the 200 tokens of
-attn_cls.hip is sais_vit_attn_cls_fwd_any.  A forward that needs gradients raises: training runs on patch 16.
+Only the ViT-S geometry is built.  A pass over the blocks (`_forward_kernels`, `_backward_kernels`) has exactly one
+of three forms, chosen once by `_pass_form`; everything that differs between them is a method of the form's class:
+- resident (`_GroupPass`): resolution groups of 224 x 224 (197 tokens) / 96 x 96 (37 tokens: DINO's local crops), a head's keys
+  and values resident in LDS (csrc/attn_vit.hip), one C call per block where it can.  Reached by `forward` at those sizes (both
+  directions), `get_last_selfattention`, `get_intermediate_layers`, `probe_features` and DINO's multi-crop pass (dino.py).
+- streaming (`_GroupPass` with `streaming`): uniform groups of any H x W in multiples of the patch size up to 4097 tokens; keys
+  and values move through LDS in tiles (csrc/attn_any.hip, backward csrc/attn_any_bwd.hip), patchify_rect.  Reached by
+  `dense_features`, `retrieval_features` and `cls_attention` (which ends in the CLS row of the last softmax, csrc/attnviz.hip) on
+  a tensor, by `forward` under grad at any other size, by a multi-crop pass with such a group, and by EVERY pass of
+  `vit_small(patch_size=8)` (ViT-S/8, inference only: the 8 x 8 gather of csrc/vit8.hip, the patch GEMM at K = 192, a 28 x 28
+  positional grid; its CLS-only last block past the 200 tokens of attn_cls.hip takes sais_vit_attn_cls_fwd_any).
+- segmented (`_SegPass`, patch 16): frames of DIFFERENT sizes, each a segment of the stacked token rows (csrc/attn_seg.hip,
+  vit_seg.SegPlan); the launch list does not depend on the number of frames or shapes.  Reached by a LIST given to
+  `dense_features`, `retrieval_features(cls_only=True)` or `forward` (under grad a training pass; without, the retrieval bits).
+DropPath (vision_transformer.py:27-46: train() only, rates linspace(0, drop_path_rate, depth)) is a per-row scale in the epilogues
+of the residual GEMMs; the keep draws come from Philox (`drop_path_seed`, this library's stream, not torch's):
+`last_droppath_scales` holds what a forward used.
 """
 import math
 import os
@@ -146,6 +140,173 @@ def _rows(t, g):
     return t if t.shape[0] == g["Fr"] * g["ntok"] else t[g["rows"]]
 
 
+class _GroupPass:
+    """The form of a pass over resolution groups: resident, or `streaming` (another patch gather and attention entry).  A form
+    owns the totals, the embedding, the DropPath draw, a block's `lse`, its attention and the norm of the CLS rows, both ways."""
+    seg = None
+
+    def __init__(self, model, rows, streaming):
+        self.m, self.streaming = model, streaming
+        self.groups, self.M, self.NP, self.Ftot = rows
+        self.resident = not streaming                    # (the streaming pass has never taken the fused-MLP switch)
+        self.one_call = not streaming and len(self.groups) == 1      # a block's C call sequences ONE group's resident attention
+
+    def record(self):                                    # in `saved`: the form for the backward, the rest for other readers
+        return {"form": self, "groups": self.groups, "M": self.M, "Ftot": self.Ftot, "streaming": self.streaming, "seg": self.seg}
+
+    def cls_only(self, save):
+        """May the last block run on the CLS rows only?  Saved: while sais_vit_attn_cls_bwd (one wave) holds every group."""
+        return not (save and any(g["ntok"] > CLS_WAVE_MAX_TOKENS for g in self.groups))
+
+    def embed_fwd(self, pl, imgs):
+        """Patchify, patch GEMM (+ bias + positional table) and CLS rows per group -> (patches bf16 [NP, K], x f32 [M, 384])."""
+        m, f, K = self.m, self.m.flat, self.m.patch_k
+        gather = ops.patchify_rect8 if m.patch == 8 else ops.patchify_rect if self.streaming else ops.patchify
+        patches, x = pl.e16(self.NP, K), pl.e32(self.M, D)
+        for im, g in zip(imgs, self.groups):
+            Fr, ntok = g["Fr"], g["ntok"]
+            pg = patches[g["prows"]]
+            xg = x[g["rows"]].view(Fr, ntok, D)
+            gather(im, pg)
+            pos, g["interp"] = m._pos_table(im.shape[2], im.shape[3], pl.dev)
+            ops.gemm_nt(pg, f.w("patch_embed.proj.weight").view(D, K), L.EPI_PATCH_F32, xg,
+                        bias=f.w32("patch_embed.proj.bias"), aux=pos, grp=(ntok - 1, ntok, 1))
+            ops.vit_cls_rows(f.w32("cls_token"), pos, xg, Fr, ntok)
+        return patches, x
+
+    def embed_bwd(self, dx, dpatch):
+        f = self.m.flat
+        for g in self.groups:
+            Fr, ntok = g["Fr"], g["ntok"]
+            dxg, dpg = dx[g["rows"]], dpatch[g["prows"]]
+            if g["interp"] is None:
+                ops.vit_embed_bwd(dxg, Fr, f.g("cls_token"), f.g("pos_embed"), dpg)
+            else:                                   # through the transpose of the bicubic map (autograd of :174-194)
+                dpos = torch.zeros(ntok, D, dtype=torch.float32, device=dx.device)
+                ops.vit_embed_bwd(dxg, Fr, f.g("cls_token"), dpos, dpg, ntok=ntok)
+                ops.pos_interp_bwd(g["interp"], dpos, f.g("pos_embed").view(NTOK, D))
+
+    def droppath_draw(self, dev):
+        """DropPath (train mode): row scales keep_f / (1 - p_i) for the 2 x depth residual branches, one Philox draw per
+        frame and branch; branch 2i = attention of block i, 2i + 1 = its MLP.  f32 [2 x depth, M]."""
+        m, parts = self.m, []
+        m._droppath_state(dev)
+        for g in self.groups:                            # one advance + draw per group (what separate passes would do)
+            ops.rng_advance(m._rng)
+            parts.append(ops.droppath_scales(m._dp_rates, g["Fr"], g["ntok"], m._rng))
+        m.last_droppath_scales = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+        return m.last_droppath_scales
+
+    def lse(self, pl):
+        return [pl.e32(g["Fr"], HEADS, g["ntok"]) if pl.save else None for g in self.groups]
+
+    def qkv_fwd(self, i, b):
+        f, p = self.m.flat, f"blocks.{i}."
+        ops.gemm_nt(b["xn1"], f.w(p + "attn.qkv.weight"), L.EPI_BIAS_BF16, b["qkv"], bias=f.w32(p + "attn.qkv.bias"))
+
+    def attn_fwd(self, pl, i, b, want_probs=False):
+        """qkv and the attention of block i per group; want_probs (get_last_selfattention): it also writes its probabilities f32
+        [frames, heads, ntok, ntok], which are returned (one group)."""
+        self.qkv_fwd(i, b)
+        probs = None
+        for g, lg in zip(self.groups, b["lse"]):
+            if want_probs:
+                probs = pl.e32(g["Fr"], HEADS, g["ntok"], g["ntok"])
+            qkv, ao = _rows(b["qkv"], g), _rows(b["ao"], g)
+            if self.streaming:
+                ops.vit_attn_fwd_any(qkv, g["Fr"], g["ntok"], ao, lg)
+            else:
+                ops.vit_attn_fwd(qkv, g["Fr"], ao, lg, probs, ntok=g["ntok"])
+        return probs
+
+    def attn_bwd(self, s, dao, dqkv):
+        for g, lg in zip(self.groups, s["lse"]):
+            r = g["rows"]
+            if self.streaming:
+                ops.vit_attn_bwd_any(s["qkv"][r], dao[r], s["ao"][r], lg, g["Fr"], g["ntok"], dqkv[r])
+            else:
+                ops.vit_attn_bwd(s["qkv"][r], dao[r], s["ao"][r], lg, None, g["Fr"], dqkv[r], ntok=g["ntok"])
+
+    def cls_norm_fwd(self, x, reps, mean=None, rstd=None):
+        """The final norm of x's CLS rows (row stride = ntok * 384) into reps [frames, 384]; returns what the norm read."""
+        for g in self.groups:
+            fr = g["frames"]
+            ops.layernorm_fwd(x[g["rows"]], g["Fr"], g["ntok"] * D, *self.m._norm_p(), y32=reps[fr],
+                              mean=None if mean is None else mean[fr], rstd=None if rstd is None else rstd[fr],
+                              ldy32=reps.stride(0))
+        return x
+
+    def cls_norm_bwd(self, saved, dreps, dx):
+        f = self.m.flat
+        for g in self.groups:
+            r, fr = g["rows"], g["frames"]
+            ops.layernorm_bwd(saved["x_final"][r], g["ntok"] * D, saved["meanN"][fr], saved["rstdN"][fr], f.w32("norm.weight"),
+                              g["Fr"], dy32=dreps[fr], dx32=dx[r], lddx32=g["ntok"] * D, dgamma=f.g("norm.weight"),
+                              dbeta=f.g("norm.bias"))
+
+
+class _SegPass(_GroupPass):
+    """The form of a segmented pass (patch 16): a streaming pass in which every frame is a segment of the stacked rows (`seg`, a
+    SegPlan on the device).  The embedding, the attention and the CLS gather / scatter are one launch each over all segments,
+    both ways, and the last block runs on every row (the one-wave CLS kernels take one token count per launch)."""
+
+    def __init__(self, model, rows, seg):
+        super().__init__(model, rows, True)
+        self.seg = seg
+
+    cls_only = staticmethod(lambda save: False)
+
+    def embed_fwd(self, pl, imgs):
+        """Four launches whatever the frames: the pixels packed, one gather, the patch GEMM with its bias, and the token rows
+        (CLS rows, patch rows + the positional table interpolated per segment from two per-axis tap matrices)."""
+        f, seg = self.m.flat, self.seg
+        pixels = imgs[0].reshape(-1) if len(imgs) == 1 else torch.cat([im.reshape(-1) for im in imgs])
+        patches, pe, x = pl.e16(self.NP, PATCH_K), pl.e32(self.NP, D), pl.e32(self.M, D)
+        ops.patchify_seg(pixels, seg, patches)
+        ops.gemm_nt(patches, f.w("patch_embed.proj.weight").view(D, PATCH_K), L.EPI_BIAS_F32, pe,
+                    bias=f.w32("patch_embed.proj.bias"))
+        ops.vit_embed_seg(pe, f.w32("cls_token"), f.w32("pos_embed"), seg, x)
+        return patches, x
+
+    def embed_bwd(self, dx, dpatch):                     # through the per-axis taps: no [hw, 196] map
+        ops.vit_embed_bwd_seg(dx, self.seg, self.m.flat.g("cls_token"), self.m.flat.g("pos_embed"), dpatch)
+
+    def droppath_draw(self, dev):
+        """ONE advance and one launch that draws per segment in list order (`last_droppath_frame_scales`, f32 [2 x depth, nseg]),
+        expanded to the rows by one more (f32 [2 x depth, M])."""
+        m = self.m
+        m._droppath_state(dev)
+        ops.rng_advance(m._rng)
+        per = m.last_droppath_frame_scales = ops.droppath_scales(m._dp_rates, self.seg.nseg, 1, m._rng)
+        m.last_droppath_scales = ops.vit_rows_expand_seg(per, self.seg)
+        return m.last_droppath_scales
+
+    def lse(self, pl):                                   # segment s owns [6, ntok] at 6 row0 of one tensor
+        return [pl.e32(HEADS * self.M) if pl.save else None]
+
+    def attn_fwd(self, pl, i, b, want_probs=False):
+        self.qkv_fwd(i, b)
+        ops.vit_attn_fwd_seg(b["qkv"], self.seg, b["ao"], b["lse"][0])
+
+    def attn_bwd(self, s, dao, dqkv):
+        ops.vit_attn_bwd_seg(s["qkv"], dao, s["ao"], s["lse"][0], self.seg, dqkv)
+
+    def cls_norm_fwd(self, x, reps, mean=None, rstd=None):
+        """The CLS rows gathered (sais_vit_cls_gather_seg), then one norm launch over them."""
+        cls = torch.empty(self.Ftot, D, dtype=torch.float32, device=x.device)      # (Ftot: one segment per frame)
+        ops.vit_cls_gather_seg(x, self.seg, cls)
+        ops.layernorm_fwd(cls, self.Ftot, D, *self.m._norm_p(), y32=reps, mean=mean, rstd=rstd, ldy32=reps.stride(0))
+        return cls
+
+    def cls_norm_bwd(self, saved, dreps, dx):
+        """On the gathered [nseg, 384] rows, then scattered to the CLS rows (sais_vit_cls_scatter_seg)."""
+        f, seg = self.m.flat, self.seg
+        dcls = torch.empty(seg.nseg, D, dtype=torch.float32, device=dx.device)
+        ops.layernorm_bwd(saved["x_final"], D, saved["meanN"], saved["rstdN"], f.w32("norm.weight"), seg.nseg, dy32=dreps,
+                          dx32=dcls, dgamma=f.g("norm.weight"), dbeta=f.g("norm.bias"))
+        ops.vit_cls_scatter_seg(dcls, seg, dx)
+
+
 class _PendingDW:
     """Weight gradients of G blocks in ONE grouped launch (ops.dw_group, LABNOTES R6.8).  A deferred block leaves here what that
     launch reads — the records of its C call (`calls`) or its four (p, q, dW, db) items (`items`) — and these keep its operands
@@ -172,10 +333,9 @@ class _ViTFn(torch.autograd.Function):
     kernels into model.flat.grad (p.grad views) as a side effect; `anchor` only keeps the node alive."""
 
     @staticmethod
-    def forward(ctx, model, x, anchor, streaming=False, seg=None):
-        reps, saved = model._forward_kernels(x, save=True, streaming=streaming, seg=seg)     # seg: x is a list, one segmented pass
-        ctx.model, ctx.saved = model, saved
-        ctx.x_requires_grad = seg is None and x.requires_grad
+    def forward(ctx, model, x, anchor, streaming=False, seg=None):       # seg: x is a list, one segmented pass
+        reps, ctx.saved = model._forward_kernels(x, save=True, streaming=streaming, seg=seg)
+        ctx.model = model
         return reps
 
     @staticmethod
@@ -260,10 +420,8 @@ class VisionTransformer(nn.Module):
     # ------------------------------------------------------------------ public API (reference signatures)
     def forward(self, x):
         """norm(x)[:, 0] (:209-214), f32 [F, 384].  x a LIST or tuple of tensors [F_i, 3, H_i, W_i] of different sizes (patch 16;
-        the checks and error texts of dense_features on a list): f32 [sum F_i, 384] in list order from ONE segmented pass over
-        all frames, whose launch list does not depend on the number of frames or shapes.  Under grad it is a training pass
-        (_forward_kernels with `seg` and `save`, every row of the last block computed; the backward is
-        sais_vit_attn_bwd_seg / sais_vit_embed_bwd_seg, csrc/attn_seg.hip); without, the bits of
+        the checks and error texts of dense_features on a list): f32 [sum F_i, 384] in list order from ONE segmented pass.
+        Under grad it is a training pass (every row of the last block computed); without, the bits of
         retrieval_features(list, cls_only=True)."""
         need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in (self.cls_token, self.norm.weight))
         if isinstance(x, (list, tuple)):
@@ -272,18 +430,15 @@ class VisionTransformer(nn.Module):
                 return self.retrieval_features(items, cls_only=True)
             self._engine(items[0].device)
             return _ViTFn.apply(self, items, self._anchor, True, self._seg_plan(items))
-        if self.patch == 8:
-            if need_grad:
-                raise NotImplementedError("the patch-8 backbone is inference only (call it under torch.no_grad() or freeze its "
-                                          "parameters): training runs on patch 16")
-            x = self._check_input(x, "forward")
-            self._engine(x.device)
-            return self._forward_kernels(x, save=False, streaming=True)[0]
-        x = self._check_input(x, "forward" if need_grad else None)      # training takes any H x W in multiples of 16
+        if self.patch == 8 and need_grad:
+            raise NotImplementedError("the patch-8 backbone is inference only (call it under torch.no_grad() or freeze its "
+                                      "parameters): training runs on patch 16")
+        # training, and a patch-8 model, take any H x W in multiples of the patch size
+        x = self._check_input(x, "forward" if need_grad or self.patch == 8 else None)
         self._engine(x.device)
         if need_grad:
             return _ViTFn.apply(self, x, self._anchor, self.streaming_pass([x]))
-        return self._forward_kernels(x, save=False)[0]
+        return self._forward_kernels(x, save=False, streaming=self.patch == 8)[0]
 
     @staticmethod
     def streaming_pass(imgs):
@@ -299,33 +454,40 @@ class VisionTransformer(nn.Module):
         self._engine(x.device)
         return self._forward_kernels(x, save=False, end="probs")[0]
 
-    def _last_norms(self, x, n, streaming):
-        """norm(x) after each of the last n blocks, oldest first, as n tensors f32 [F, ntok, 384]: every row of every block, and
-        the residual stream is updated in place, so each is normalised before the next block runs."""
+    def _last_norms(self, x, n, streaming, view=None):
+        """norm(x) after each of the last n blocks, oldest first, each normalised (one launch, f32 [M, 384]) before the next block
+        overwrites the stream: n tensors [F, ntok, 384]; x a checked list (one segmented pass): n times view(stacked tensor)."""
+        first, out, Fr = self.depth - self._check_n(n), [], len(x)
+        view = view or (lambda y: y.view(Fr, -1, D))
+
+        def tap(i, xs):
+            if i >= first:
+                y = torch.empty(xs.shape[0], D, dtype=torch.float32, device=xs.device)
+                ops.layernorm_fwd(xs, xs.shape[0], D, *self._norm_p(), y32=y)
+                out.append(view(y))
+        self._engine(x[0].device if isinstance(x, list) else x.device)
+        self._forward_kernels(x, save=False, end="blocks", tap=tap, streaming=streaming,
+                              seg=self._seg_plan(x) if isinstance(x, list) else None)
+        return out
+
+    def _check_n(self, n):
         n = int(n)
         if not 1 <= n <= self.depth:
             raise ValueError(f"n = {n} must be in [1, {self.depth}]")
-        f, Fr, out = self._engine(x.device), x.shape[0], []
+        return n
 
-        def tap(i, xs):
-            if i >= self.depth - n:
-                y = torch.empty(Fr, xs.shape[0] // Fr, D, dtype=torch.float32, device=x.device)
-                ops.layernorm_fwd(xs, xs.shape[0], D, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6, y32=y)
-                out.append(y)
-        self._forward_kernels(x, save=False, end="blocks", tap=tap, streaming=streaming)
-        return out
+    def _norm_p(self):                               # the final LayerNorm's (gamma, beta, eps)
+        return self.flat.w32("norm.weight"), self.flat.w32("norm.bias"), 1e-6
 
     @torch.no_grad()
     def get_intermediate_layers(self, x, n=1):
         """vision_transformer.py:225-233: norm(x) after each of the last n blocks, oldest first, as n tensors f32
         [F, 197, 384].  Inference only (runs under no_grad, nothing is saved for a backward); 224 x 224 frames only.  Every row
         of the last block is computed (no CLS-only tail)."""
-        if self.patch == 8:                          # any size, as dense_features
-            return self._last_norms(self._check_input(x, "get_intermediate_layers"), n, streaming=True)
-        x = self._check_input(x)
-        if x.shape[-1] != 224:
+        x = self._check_input(x, "get_intermediate_layers" if self.patch == 8 else None)      # patch 8: any size
+        if self.patch != 8 and x.shape[-1] != 224:
             raise ValueError("get_intermediate_layers takes 224 x 224 frames")
-        return self._last_norms(x, n, streaming=False)
+        return self._last_norms(x, n, streaming=self.patch == 8)
 
     @torch.no_grad()
     def probe_features(self, x, n=4, avgpool=False):
@@ -342,24 +504,21 @@ class VisionTransformer(nn.Module):
         x = self._check_input(x, "probe_features" if streaming else None)
         if not streaming and x.shape[-1] != 224:
             raise ValueError("probe_features takes 224 x 224 frames")
-        if not 1 <= n <= self.depth:
-            raise ValueError(f"n = {n} must be in [1, {self.depth}]")
-        f, Fr = self._engine(x.device), x.shape[0]
-        ntok = 1 + (x.shape[2] // self.patch) * (x.shape[3] // self.patch)
+        n = self._check_n(n)
+        self._engine(x.device)
+        Fr, ntok = x.shape[0], 1 + (x.shape[2] // self.patch) * (x.shape[3] // self.patch)
         if avgpool:
             xs = self._forward_kernels(x, save=False, end="blocks", streaming=streaming)[0]
             feats = torch.empty(Fr, 2 * D, dtype=torch.float32, device=x.device)
-            ops.vit_cls_avgpool_norm(xs, Fr, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6, feats, ntok=ntok)
+            ops.vit_cls_avgpool_norm(xs, Fr, *self._norm_p(), feats, ntok=ntok)
             return feats
         if n == 1:
             return self._forward_kernels(x, save=False, streaming=streaming)[0]
-        feats = torch.empty(Fr, D * n, dtype=torch.float32, device=x.device)
-        first = self.depth - n
+        feats, first = torch.empty(Fr, D * n, dtype=torch.float32, device=x.device), self.depth - n
 
         def tap(i, xs):            # slots of the earlier blocks; the last slot is written by the pass itself (reps_out)
             if first <= i < self.depth - 1:
-                ops.layernorm_fwd(xs, Fr, ntok * D, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6,
-                                  y32=feats[:, (i - first) * D:], ldy32=D * n)
+                ops.layernorm_fwd(xs, Fr, ntok * D, *self._norm_p(), y32=feats[:, (i - first) * D:], ldy32=D * n)
         self._forward_kernels(x, save=False, tap=tap, reps_out=feats[:, (n - 1) * D:], streaming=streaming)
         return feats
 
@@ -367,19 +526,16 @@ class VisionTransformer(nn.Module):
     def dense_features(self, x, n=1):
         """get_intermediate_layers (vision_transformer.py:225-233) at ANY resolution: x f32 [F, 3, H, W] on the device, H and W
         multiples of 16 (not necessarily equal), 1 + (H/16)(W/16) <= 4097 tokens.  Returns n tensors f32 [F, 1 + hw, 384],
-        oldest first: norm(x) after each of the last n blocks.  Inference only, every row of every block is computed.  The
-        launch list of forward() (_forward_kernels) with `streaming`: patchify_rect, the patch GEMM with the positional table
-        interpolated to (H, W) (interpolate_pos_encoding :174-194), then per block the row-generic GEMM / LayerNorm kernels
-        around the streaming attention (sais_vit_attn_fwd_any).  A 224 x 224 input takes these kernels too
-        (dino-main/eval_video_segmentation.py runs it at 480 x 832: 1561 tokens).
+        oldest first: norm(x) after each of the last n blocks.  Inference only, every row of every block is computed, in a
+        streaming pass (a 224 x 224 input too; dino-main/eval_video_segmentation.py runs it at 480 x 832: 1561 tokens).
         x a LIST or tuple of such tensors [F_i, 3, H_i, W_i] of different sizes (patch 16 only): ONE segmented pass over all
-        frames (every frame a segment of the stacked rows: sais_patchify_seg, the patch GEMM, sais_vit_embed_seg, then per block
-        the same row-generic launches around one sais_vit_attn_fwd_seg, csrc/attn_seg.hip), whose launch list does not depend on
-        the number of frames or shapes.  Returns per requested layer a list of [F_i, 1 + hw_i, 384] views.  The checks and
-        error texts are the single tensor's, per item; an empty list raises."""
-        if isinstance(x, (list, tuple)):
-            return self._dense_features_list(x, n)
-        return self._last_norms(self._check_input(x, "dense_features"), n, streaming=True)
+        frames.  Returns per requested layer a list of [F_i, 1 + hw_i, 384] views of one stacked tensor.  The checks and error
+        texts are the single tensor's, per item; an empty list raises."""
+        if not isinstance(x, (list, tuple)):
+            return self._last_norms(self._check_input(x, "dense_features"), n, streaming=True)
+        items = self._check_list(x, "dense_features")
+        groups = _row_groups(items, self.patch)[0]
+        return self._last_norms(items, n, True, lambda y: [y[g["rows"]].view(g["Fr"], g["ntok"], D) for g in groups])
 
     def _check_list(self, items, name):
         """A list of device tensors [F_i, 3, H_i, W_i] for one segmented pass: _check_input per item, with its errors."""
@@ -389,24 +545,6 @@ class VisionTransformer(nn.Module):
         if len(items) == 0:
             raise ValueError(f"VisionTransformer.{name}: an empty list of frames")
         return [self._check_input(x, name) for x in items]
-
-    def _dense_features_list(self, items, n):
-        """dense_features on a list: one segmented pass; per requested layer a list of [F_i, 1 + hw_i, 384] views of one
-        stacked tensor."""
-        items = self._check_list(items, "dense_features")
-        n = int(n)
-        if not 1 <= n <= self.depth:
-            raise ValueError(f"n = {n} must be in [1, {self.depth}]")
-        f, out = self._engine(items[0].device), []
-        groups = _row_groups(items, self.patch)[0]
-
-        def tap(i, xs):
-            if i >= self.depth - n:
-                y = torch.empty(xs.shape[0], D, dtype=torch.float32, device=xs.device)
-                ops.layernorm_fwd(xs, xs.shape[0], D, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6, y32=y)
-                out.append([y[g["rows"]].view(g["Fr"], g["ntok"], D) for g in groups])
-        self._forward_kernels(items, save=False, end="blocks", tap=tap, streaming=True, seg=self._seg_plan(items))
-        return out
 
     @staticmethod
     def _seg_plan(items):
@@ -421,36 +559,25 @@ class VisionTransformer(nn.Module):
         pooling with exponent 4 of its patch tokens clamped at 1e-6 — the reference's torch.cat(dim=1), concatenated, not
         interleaved.  Inference only.  Launches: dense_features' for every block, then sais_vit_cls_gem_norm on the residual
         stream: the normed [F, N, 384] tensor is never written.  cls_only: f32 [F, 384], the first half alone (what
-        eval_image_retrieval.py reads: model(x) at any resolution) — the blocks, then one sais_layernorm_fwd launch over the CLS
-        rows, which is the launch that writes the first half of the full descriptor, so the bits are the same; no GeM pass.
+        eval_image_retrieval.py reads: model(x) at any resolution) — the blocks, then the form's norm over the CLS rows (the
+        launch that writes the first half of the full descriptor, so the bits are the same); no GeM pass.
         x a LIST or tuple of tensors [F_i, 3, H_i, W_i] of different sizes (patch 16, cls_only=True only; the GeM half over
-        segments is not built): one segmented pass as dense_features runs it on a list, then sais_vit_cls_gather_seg and the
-        same sais_layernorm_fwd launch over the gathered CLS rows: f32 [sum F_i, 384] in list order.  A frame's row agrees with
-        the single-tensor call up to the rounding of the batch-dependent GEMM tiling and of the separable positional
-        interpolation (sixteen f32 terms instead of one f32 GEMM row)."""
-        if isinstance(x, (list, tuple)):
-            # frames of different sizes: one segmented pass, then the CLS rows gathered for the same sais_layernorm_fwd launch
-            items = self._check_list(x, "retrieval_features")
-            if not cls_only:
-                raise NotImplementedError("retrieval_features on a list returns the CLS half only (cls_only=True): the GeM "
-                                          "pooling over segments of different sizes is not built")
-            f, seg = self._engine(items[0].device), self._seg_plan(items)
-            xs = self._forward_kernels(items, save=False, end="blocks", streaming=True, seg=seg)[0]
-            cls = torch.empty(seg.nseg, D, dtype=torch.float32, device=xs.device)
-            feats = torch.empty_like(cls)
-            ops.vit_cls_gather_seg(xs, seg, cls)
-            ops.layernorm_fwd(cls, seg.nseg, D, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6, y32=feats)
-            return feats
-        x = self._check_input(x, "retrieval_features")
-        f, Fr = self._engine(x.device), x.shape[0]
-        xs = self._forward_kernels(x, save=False, end="blocks", streaming=True)[0]
-        ntok = xs.shape[0] // Fr
-        if cls_only:
-            feats = torch.empty(Fr, D, dtype=torch.float32, device=x.device)
-            ops.layernorm_fwd(xs, Fr, ntok * D, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6, y32=feats)
-            return feats
-        feats = torch.empty(Fr, 2 * D, dtype=torch.float32, device=x.device)
-        ops.vit_cls_gem_norm(xs, Fr, ntok, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6, feats)
+        segments is not built): one segmented pass, then its norm over the gathered CLS rows: f32 [sum F_i, 384] in list order.
+        A frame's row agrees with the single-tensor call up to the rounding of the batch-dependent GEMM tiling and of the
+        separable positional interpolation (sixteen f32 terms instead of one f32 GEMM row)."""
+        many = isinstance(x, (list, tuple))
+        x = self._check_list(x, "retrieval_features") if many else self._check_input(x, "retrieval_features")
+        if many and not cls_only:
+            raise NotImplementedError("retrieval_features on a list returns the CLS half only (cls_only=True): the GeM "
+                                      "pooling over segments of different sizes is not built")
+        self._engine(x[0].device if many else x.device)
+        form, imgs = self._pass_form(x, True, self._seg_plan(x) if many else None, "blocks")
+        xs = self._pass(form, imgs, False, "blocks")[0]
+        feats = torch.empty(form.Ftot, D if cls_only else 2 * D, dtype=torch.float32, device=xs.device)
+        if cls_only:                                 # every row of the last block, then the form's norm over the CLS rows
+            form.cls_norm_fwd(xs, feats)
+        else:
+            ops.vit_cls_gem_norm(xs, form.Ftot, form.groups[0]["ntok"], *self._norm_p(), feats)
         return feats
 
     @torch.no_grad()
@@ -460,8 +587,7 @@ class VisionTransformer(nn.Module):
         tokens, the CLS key included — what video_generation.py and visualize_attention.py read.  Inference only.  Launches:
         dense_features' for every block but the last, then the last block's norm1, the K third of its qkv GEMM over all rows,
         the Q third over the CLS rows only and sais_vit_cls_probs: no V, no attention output, no proj, no MLP, and no
-        [F, 6, N, N] tensor.  A 224 x 224 input takes this path too.  (The full N x N probabilities off 224 x 224 are not built:
-        nothing in the reference reads them.)"""
+        [F, 6, N, N] tensor (off 224 x 224 / 96 x 96 that one is not built: nothing in the reference reads it)."""
         x = self._check_input(x, "cls_attention")
         f, dev, Fr = self._engine(x.device), x.device, x.shape[0]
         xn = self._forward_kernels(x, save=False, end="norm1", streaming=True)[0]
@@ -516,58 +642,53 @@ class VisionTransformer(nn.Module):
     def _forward_kernels(self, img, save, end="reps", tap=None, reps_out=None, streaming=False, seg=None):
         """img: one [F,3,H,W] tensor, or a LIST of them with different sizes (DINO's multi-crop student, utils.py:611-630):
         the groups are then stacked along the token-row axis and every GEMM / LayerNorm of a block runs ONCE over all rows
-        (only attention, the embedding glue and the final CLS gather are per group) — 44 160 rows in one launch fill the
-        chip where 25 216 + 18 944 in two launches leave workgroup slots empty.  Returns (result, saved).  `end` names where
-        the pass stops and what the result is: "reps": after the final norm, reps f32 [sum F, 384] in group order; "probs":
-        in the last block's attention, its probabilities (get_last_selfattention); "norm1": at the last block's norm1, its bf16
-        output [M, 384] (cls_attention); "blocks": after the last block, the residual stream f32 [M, 384], every row computed
-        and no final norm.  streaming: any H x W in multiples of 16: patchify_rect and the attention that streams keys
-        and values through LDS instead of the kernels instantiated for SIDES, in every group; with `save` the attention also
-        writes its log-sum-exp and the backward takes sais_vit_attn_bwd_any (the decision is recorded in `saved`).  A streaming
-        pass has no block-level C call and no fused-MLP kernel, in either direction.  tap(i, x): called
-        after every block but a CLS-only last one with the residual stream the block left (without `save` the next block
-        overwrites it); reps_out: a [sum F, 384] view (any row stride) that receives reps instead of a new tensor.
-        seg (patch 16, streaming, end="blocks" or "reps"): the pass's SegPlan (_seg_plan): every FRAME of every item is a segment
-        of the stacked rows and the embedding and the attention are one launch each over all segments
-        (csrc/attn_seg.hip): the launch list does not depend on the number of frames or shapes.  end="reps": the CLS rows
-        gathered (sais_vit_cls_gather_seg) for one final-norm launch; the last block runs on every row (the one-wave CLS
-        kernels take one token count per launch).  With `save` the attention keeps its log-sum-exp ([6, ntok] at 6 row0 of one
-        f32 [6 M] tensor per block), DropPath is drawn per segment in list order, and `saved` records the plan: the backward
-        follows it (sais_vit_attn_bwd_seg, sais_vit_embed_bwd_seg: no per-shape launch in either direction)."""
-        f = self.flat
+        (44 160 rows in one launch fill the chip where 25 216 + 18 944 in two leave workgroup slots empty; what is per group is
+        the form's).  Returns (result, saved).  `end` names where the pass stops and what the result is: "reps": after the
+        final norm, reps f32 [sum F, 384] in group order; "probs": in the last block's attention, its probabilities
+        (get_last_selfattention); "norm1": at the last block's norm1, its bf16 output [M, 384] (cls_attention); "blocks": after
+        the last block, the residual stream f32 [M, 384], every row computed and no final norm.  tap(i, x): called after every
+        block but a CLS-only last one with the residual stream the block left (without `save` the next block overwrites it);
+        reps_out: a [sum F, 384] view (any row stride) that receives reps instead of a new tensor.  streaming, seg: which form
+        the pass has (_pass_form; the module docstring); `saved` records the form and the backward follows it.  A streaming
+        or segmented pass has no block-level C call and no fused-MLP kernel, in either direction."""
+        form, imgs = self._pass_form(img, streaming, seg, end)
+        return self._pass(form, imgs, save, end, tap, reps_out)
+
+    def _pass_form(self, img, streaming, seg, end):
+        """(the form of the pass `_forward_kernels` was asked for, its inputs as a list): the one place that tells resident,
+        streaming and segmented apart, and the one that refuses an impossible combination."""
         imgs = list(img) if isinstance(img, (list, tuple)) else [img]
-        dev = imgs[0].device
-        groups, M, NP, Ftot = _row_groups(imgs, self.patch)
-        if end == "probs" and len(groups) > 1:
+        rows = _row_groups(imgs, self.patch)
+        if end == "probs" and len(rows[0]) > 1:
             raise ValueError("get_last_selfattention takes one resolution")
-        # Every decision of the pass, taken once; inside the loop only "is this the last block" is left.
-        pl = SimpleNamespace(groups=groups, M=M, NP=NP, Ftot=Ftot, dev=dev, save=save, e16=_empty(torch.bfloat16, dev),
-                             e32=_empty(torch.float32, dev), streaming=streaming, reps_out=reps_out, seg=seg)
-        if seg is not None and (end not in ("blocks", "reps") or not streaming or self.patch != 16 or seg.M != M):
+        if seg is None:
+            return _GroupPass(self, rows, streaming), imgs
+        if end not in ("blocks", "reps") or not streaming or self.patch != 16 or seg.M != rows[1]:
             raise NotImplementedError("the segmented pass is the patch-16 streaming pass to the last block or the final norm")
-        # Large M (training step, big extraction batches): the N = 384 GEMMs run on the row-owning kernel with the
-        # FOLLOWING LayerNorm in their epilogue (sais_gemm_ln_fwd): proj -> norm2, fc2 -> the next block's norm1.
-        # Only block 0's norm1 and the final norm remain stand-alone launches.
+        return _SegPass(self, rows, seg), imgs
+
+    def _pass(self, form, imgs, save, end="reps", tap=None, reps_out=None):
+        """_forward_kernels on a form."""
+        f, dev, groups, M, Ftot = self.flat, imgs[0].device, form.groups, form.M, form.Ftot
+        # Every decision of the pass, taken once; inside the loop only "is this the last block" is left.
+        pl = SimpleNamespace(form=form, groups=groups, M=M, Ftot=Ftot, dev=dev, save=save, e16=_empty(torch.bfloat16, dev),
+                             e32=_empty(torch.float32, dev), reps_out=reps_out)
+        # Large M (training step, big extraction batches): the N = 384 GEMMs run on the row-owning kernel with the FOLLOWING
+        # LayerNorm in their epilogue (sais_gemm_ln_fwd: proj -> norm2, fc2 -> next norm1); block 0's norm1 and the final norm stay
         pl.fused = fused = M >= ops.ROW_GEMM_MIN_M
         # the CLS-only tail runs its [frames, 384] GEMMs on the split-K small-M kernel (SAIS_EPI_RAW_SLABS_F32: M < 8192 only), so a
-        # pass with 8192 or more FRAMES computes the last block on every row like the others (ADVICE r4; pruned=False is
-        # recorded in `saved`, the backward follows it)
-        # and a pass that is saved for a backward keeps the CLS-only tail only while sais_vit_attn_cls_bwd holds every group (one wave
-        # per (frame, head): CLS_WAVE_MAX_TOKENS); past it the last block is computed on every row
-        pl.prune = end == "reps" and self.prune_last_block and Ftot < ops.ROW_GEMM_MIN_M and seg is None and \
-            not (save and any(g["ntok"] > CLS_WAVE_MAX_TOKENS for g in groups))
+        # pass with 8192 or more FRAMES computes the last block on every row like the others (ADVICE r4; `saved` records
+        # pruned=False, the backward follows it), and so does a form without a CLS-only tail for this pass (form.cls_only)
+        pl.prune = end == "reps" and self.prune_last_block and Ftot < ops.ROW_GEMM_MIN_M and form.cls_only(save)
         pl.prune_q = pl.prune and len(groups) == 1 and _PRUNE_Q
-        pl.mlp_fused = not streaming and ops.mlp_fused_enabled(M)      # (the streaming pass has never taken that switch)
-        # One C call per Block (sais_vit_block_fwd: the launches of _block_fwd_launches, sequenced by the library) whenever
-        # nothing needs the per-launch view: no HIP-event instrumentation (bench.py's roofline pass), one resolution group
-        # (and not the block whose probabilities get_last_selfattention returns); it sequences the resident attention
-        pl.block_call = self.block_calls and ops.TIMER is None and len(groups) == 1 and fused and not pl.mlp_fused \
-            and not streaming
-        patches, x = self._embed_fwd(pl, imgs)
+        pl.mlp_fused = form.resident and ops.mlp_fused_enabled(M)
+        # One C call per Block (sais_vit_block_fwd: the launches of _block_fwd_launches, sequenced by the library) whenever nothing
+        # needs the per-launch view: no HIP-event instrumentation (bench.py's roofline pass), a form that has one
+        pl.block_call = self.block_calls and ops.TIMER is None and form.one_call and fused and not pl.mlp_fused
+        patches, x = form.embed_fwd(pl, imgs)
         draw = self.training and self.drop_path_rate > 0 and end != "probs"
-        pl.dp = dp = (self._droppath_draw(groups, dev) if seg is None else self._droppath_draw_seg(seg, dev)) if draw else None
-        saved = {"patches": patches, "blocks": [], "groups": groups, "M": M, "Ftot": Ftot, "dp": dp, "streaming": streaming,
-                 "pruned": False, "seg": seg} if save else None
+        pl.dp = dp = form.droppath_draw(dev) if draw else None
+        saved = dict(form.record(), patches=patches, blocks=[], dp=dp, pruned=False) if save else None
         b = ln1 = None                                   # the block's tensors; (xn, mean1, rstd1) of its norm1
         # norm1's outputs for a block: its own with `save`, else one xn for the whole pass and no statistics
         norm1_out = lambda: (pl.e16(M, D), pl.e32(M), pl.e32(M)) if save else ln1 or (pl.e16(M, D), None, None)
@@ -601,7 +722,7 @@ class VisionTransformer(nn.Module):
             if save or b is None:                        # without `save` one set of tensors serves every block
                 b = self._block_buffers(pl, x, ln1)
             if end == "probs" and last:
-                return self._attn_fwd(pl, i, b, want_probs=True), None
+                return form.attn_fwd(pl, i, b, want_probs=True), None
             nxt = norm1_out() if fused and not last else None
             x_out = pl.e32(M, D) if save else x          # (without `save` the residual stream is updated in place)
             rs_attn, rs_mlp = (None, None) if dp is None else (dp[2 * i], dp[2 * i + 1])
@@ -620,43 +741,12 @@ class VisionTransformer(nn.Module):
                 tap(i, x)
         if end == "blocks":
             return x, saved
-        reps, meanN, rstdN, x_final = self._final_norm_fwd(pl, x)      # x_final: what the norm read (the gathered CLS rows or x)
+        reps = pl.e32(Ftot, D) if reps_out is None else reps_out
+        meanN, rstdN = (pl.e32(Ftot), pl.e32(Ftot)) if save else (None, None)
+        x_final = form.cls_norm_fwd(x, reps, meanN, rstdN)      # what the norm read (the gathered CLS rows or x)
         if save:
             saved.update(x_final=x_final, meanN=meanN, rstdN=rstdN)
         return reps, saved
-
-    def _embed_fwd(self, pl, imgs):
-        """Patchify, patch GEMM (+ bias + positional table) and CLS rows per group -> (patches bf16 [NP, 768], x f32 [M, 384]);
-        a patch-8 model (streaming only): the 8 x 8 gather and K = 192."""
-        f, K = self.flat, self.patch_k
-        if pl.seg is not None:
-            return self._embed_fwd_seg(pl, imgs)
-        gather = ops.patchify_rect8 if self.patch == 8 else ops.patchify_rect if pl.streaming else ops.patchify
-        patches = pl.e16(pl.NP, K)
-        x = pl.e32(pl.M, D)
-        for im, g in zip(imgs, pl.groups):
-            Fr, ntok = g["Fr"], g["ntok"]
-            pg = patches[g["prows"]]
-            xg = x[g["rows"]].view(Fr, ntok, D)
-            gather(im, pg)
-            pos, g["interp"] = self._pos_table(im.shape[2], im.shape[3], pl.dev)
-            ops.gemm_nt(pg, f.w("patch_embed.proj.weight").view(D, K), L.EPI_PATCH_F32, xg,
-                        bias=f.w32("patch_embed.proj.bias"), aux=pos, grp=(ntok - 1, ntok, 1))
-            ops.vit_cls_rows(f.w32("cls_token"), pos, xg, Fr, ntok)
-        return patches, x
-
-    def _embed_fwd_seg(self, pl, imgs):
-        """_embed_fwd of a segmented pass, four launches whatever the frames: the pixels packed, one gather, the patch GEMM with
-        its bias over all patch rows, and the token rows (CLS rows, patch rows + the positional table interpolated per segment
-        from two per-axis tap matrices: no [hw, 196] map per shape)."""
-        f, seg = self.flat, pl.seg
-        pixels = imgs[0].reshape(-1) if len(imgs) == 1 else torch.cat([im.reshape(-1) for im in imgs])
-        patches, pe, x = pl.e16(pl.NP, PATCH_K), pl.e32(pl.NP, D), pl.e32(pl.M, D)
-        ops.patchify_seg(pixels, seg, patches)
-        ops.gemm_nt(patches, f.w("patch_embed.proj.weight").view(D, PATCH_K), L.EPI_BIAS_F32, pe,
-                    bias=f.w32("patch_embed.proj.bias"))
-        ops.vit_embed_seg(pe, f.w32("cls_token"), f.w32("pos_embed"), seg, x)
-        return patches, x
 
     def _droppath_state(self, dev):
         """The Philox state and the per-branch rates on the device, made on first use."""
@@ -665,62 +755,22 @@ class VisionTransformer(nn.Module):
             rates = torch.linspace(0, self.drop_path_rate, self.depth).repeat_interleave(2)      # :150
             self._dp_rates = rates.to(dev, torch.float32)
 
-    def _droppath_draw(self, groups, dev):
-        """DropPath (train mode): row scales keep_f / (1 - p_i) for the 2 x depth residual branches, one Philox draw per
-        frame and branch; branch 2i = attention of block i, 2i + 1 = its MLP.  f32 [2 x depth, M]."""
-        self._droppath_state(dev)
-        parts = []
-        for g in groups:                                 # one advance + draw per group (what separate passes would do)
-            ops.rng_advance(self._rng)
-            parts.append(ops.droppath_scales(self._dp_rates, g["Fr"], g["ntok"], self._rng))
-        dp = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
-        self.last_droppath_scales = dp
-        return dp
-
-    def _droppath_draw_seg(self, seg, dev):
-        """_droppath_draw of a segmented pass: ONE advance and one launch that draws per segment in list order
-        (`last_droppath_frame_scales`, f32 [2 x depth, nseg]), expanded to the rows by one more (f32 [2 x depth, M])."""
-        self._droppath_state(dev)
-        ops.rng_advance(self._rng)
-        per = self.last_droppath_frame_scales = ops.droppath_scales(self._dp_rates, seg.nseg, 1, self._rng)
-        dp = self.last_droppath_scales = ops.vit_rows_expand_seg(per, seg)
-        return dp
-
     @staticmethod
     def _block_buffers(pl, x, ln1):
         """The tensors of one block, for the C call or the launch list; with `save` this dict is what the backward gets.  Without,
         the stream is updated in place and only the launch list needs h (the C call keeps GELU(u) in its workspace)."""
         M, save, e16, e32 = pl.M, pl.save, pl.e16, pl.e32
         return dict(x_in=x, mean1=ln1[1], rstd1=ln1[2], xn1=ln1[0], qkv=e16(M, 3 * D), ao=e16(M, D),
-                    lse=[e32(HEADS * M) if save else None] if pl.seg is not None else
-                    [e32(g["Fr"], HEADS, g["ntok"]) if save else None for g in pl.groups],
-                    x_mid=e32(M, D) if save else x, mean2=e32(M) if save else None, rstd2=e32(M) if save else None,
+                    lse=pl.form.lse(pl), x_mid=e32(M, D) if save else x, mean2=e32(M) if save else None,
+                    rstd2=e32(M) if save else None,
                     xn2=e16(M, D), dgelu=ops.gelu_grad_buffer(M, HID, pl.dev) if save else None,
                     h=e16(M, HID) if save or not pl.block_call else None)
-
-    def _attn_fwd(self, pl, i, b, want_probs=False):
-        """qkv and the attention of block i, per group: LDS-resident, or (pl.streaming) the one that takes any token count.  want_probs: get_last_selfattention's exit — the attention also writes
-        its probabilities f32 [frames, heads, ntok, ntok], which are returned (one group)."""
-        f, p, probs = self.flat, f"blocks.{i}.", None
-        ops.gemm_nt(b["xn1"], f.w(p + "attn.qkv.weight"), L.EPI_BIAS_BF16, b["qkv"], bias=f.w32(p + "attn.qkv.bias"))
-        if pl.seg is not None:                           # every frame of the pass in one launch
-            ops.vit_attn_fwd_seg(b["qkv"], pl.seg, b["ao"], b["lse"][0])
-            return None
-        for g, lg in zip(pl.groups, b["lse"]):
-            if want_probs:
-                probs = pl.e32(g["Fr"], HEADS, g["ntok"], g["ntok"])
-            qkv, ao = _rows(b["qkv"], g), _rows(b["ao"], g)
-            if pl.streaming:
-                ops.vit_attn_fwd_any(qkv, g["Fr"], g["ntok"], ao, lg)
-            else:
-                ops.vit_attn_fwd(qkv, g["Fr"], ao, lg, probs, ntok=g["ntok"])
-        return probs
 
     def _block_fwd_launches(self, pl, i, b, x_out, nxt, rs_attn, rs_mlp):
         """One block as its launches; nxt: where fc2's epilogue puts the next block's norm1, or None."""
         f, p, M, save = self.flat, f"blocks.{i}.", pl.M, pl.save
         x, x_mid, xn2, h, u = b["x_in"], b["x_mid"], b["xn2"], b["h"], b["dgelu"]
-        self._attn_fwd(pl, i, b)
+        pl.form.attn_fwd(pl, i, b)
         if pl.fused:
             ops.gemm_ln_fwd(b["ao"], f.w(p + "attn.proj.weight"), f.w32(p + "attn.proj.bias"), x, x_mid, xn2,
                             f.w32(p + "norm2.weight"), f.w32(p + "norm2.bias"), 1e-6, b["mean2"], b["rstd2"], rowscale=rs_attn)
@@ -747,25 +797,6 @@ class VisionTransformer(nn.Module):
             else:
                 ops.gemm_nt(h, f.w(p + "mlp.fc2.weight"), L.EPI_BIAS_RESID_F32, x_out, bias=f.w32(p + "mlp.fc2.bias"),
                             aux=x_mid, rowscale=rs_mlp)
-
-    def _final_norm_fwd(self, pl, x):
-        """The final norm on the CLS rows only (row stride = ntok * 384; a segmented pass gathers them first).  Returns
-        (reps f32 [frames, 384], mean, rstd, the tensor the norm read)."""
-        f, Ftot = self.flat, pl.Ftot
-        reps = pl.e32(Ftot, D) if pl.reps_out is None else pl.reps_out
-        meanN, rstdN = (pl.e32(Ftot), pl.e32(Ftot)) if pl.save else (None, None)
-        if pl.seg is not None:                           # the CLS rows gathered, then the launch of retrieval_features(list)
-            cls = pl.e32(Ftot, D)
-            ops.vit_cls_gather_seg(x, pl.seg, cls)
-            ops.layernorm_fwd(cls, Ftot, D, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6, y32=reps, mean=meanN, rstd=rstdN,
-                              ldy32=reps.stride(0))
-            return reps, meanN, rstdN, cls
-        for g in pl.groups:
-            fr = g["frames"]
-            ops.layernorm_fwd(x[g["rows"]], g["Fr"], g["ntok"] * D, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6,
-                              y32=reps[fr], mean=None if meanN is None else meanN[fr],
-                              rstd=None if rstdN is None else rstdN[fr], ldy32=reps.stride(0))
-        return reps, meanN, rstdN, x
 
     def _block_params(self, i):
         """ctypes parameter blocks of the Blocks (pointers into the flat buffers), rebuilt when those are."""
@@ -807,8 +838,7 @@ class VisionTransformer(nn.Module):
                            out32=x_out)
         reps = e32(Ftot, D) if pl.reps_out is None else pl.reps_out
         meanN, rstdN = (e32(Ftot), e32(Ftot)) if save else (None, None)
-        ops.layernorm_fwd(x_out, Ftot, D, f.w32("norm.weight"), f.w32("norm.bias"), 1e-6, y32=reps, mean=meanN, rstd=rstdN,
-                          ldy32=reps.stride(0))
+        ops.layernorm_fwd(x_out, Ftot, D, *self._norm_p(), y32=reps, mean=meanN, rstd=rstdN, ldy32=reps.stride(0))
         tail = dict(cls=True, x_in=x, mean1=ln1[1], rstd1=ln1[2], xn1=ln1[0], qkv=qkv, ao=ao, x_mid=x_mid, mean2=mean2, rstd2=rstd2,
                     xn2=xn2, dgelu=u, h=h, rs_attn=rs_attn, rs_mlp=rs_mlp, x_out=x_out, meanN=meanN, rstdN=rstdN) if save else None
         return reps, tail
@@ -857,7 +887,7 @@ class VisionTransformer(nn.Module):
         else:
             ops.gemm_tn_grouped(compact, Ftot)
             ops.gemm_tn_grouped([(dqkv, s["xn1"], gW, gb)], M)
-        dp = saved.get("dp")
+        dp = saved["dp"]
         rs_prev = None if dp is None or i == 0 else dp[2 * (i - 1) + 1]
         if pl.fused and all(g["Fr"] * g["ntok"] >= ops.ROW_GEMM_MIN_M for g in groups):
             for g in groups:
@@ -891,20 +921,18 @@ class VisionTransformer(nn.Module):
         f = self.flat
         f.attach_grads()
         dev = dreps.device
-        groups, M, dp = saved["groups"], saved["M"], saved.get("dp")
-        e16 = _empty(torch.bfloat16, dev)
+        form, dp, pruned = saved["form"], saved["dp"], saved["pruned"]      # (what the forward recorded)
+        groups, M, e16 = form.groups, form.M, _empty(torch.bfloat16, dev)
         # Every decision of the pass, taken once (from this pass's own inputs, not from what the forward decided).
-        pruned, streaming = bool(saved.get("pruned")), bool(saved.get("streaming"))      # (what the forward recorded)
         fused = M >= ops.ROW_GEMM_MIN_M
-        mlp_fused = not streaming and ops.mlp_fused_enabled(M)
-        block_call = self.block_calls and ops.TIMER is None and len(groups) == 1 and fused and not mlp_fused and not streaming
+        mlp_fused = form.resident and ops.mlp_fused_enabled(M)
+        block_call = self.block_calls and ops.TIMER is None and form.one_call and fused and not mlp_fused
         # a data-parallel hook that all-reduces the blocks' gradients while the backward goes on (an idle one — GradSync in a world
         # of one — carries active = False)
         hooked = self.grad_ready_hook is not None and getattr(self.grad_ready_hook, "active", True)
         # blocks per weight-gradient launch (_PendingDW); 1: every block launches its own
         G = ops.dw_group(dp_hooks=hooked) if fused and M % 32 == 0 and not mlp_fused else 1
-        pl = SimpleNamespace(groups=groups, M=M, e16=e16, fused=fused, mlp_fused=mlp_fused, defer=G > 1, streaming=streaming,
-                             seg=saved.get("seg"))
+        pl = SimpleNamespace(form=form, groups=groups, M=M, e16=e16, fused=fused, mlp_fused=mlp_fused, defer=G > 1)
         pend = _PendingDW(self, saved, G, hooked)
         dxa = e16(M, D)                            # bf16 copy of the residual-stream gradient that enters a block
         # scratch of the launch list (the C call has its workspace; dqkv also serves the CLS-only block): dxb = the bf16 gradient at
@@ -918,7 +946,7 @@ class VisionTransformer(nn.Module):
             self._cls_tail_bwd(pl, saved, dreps, dx, dxa, t.dqkv, pend)
         else:
             dx = torch.zeros(M, D, dtype=torch.float32, device=dev)
-            self._final_norm_bwd(saved, dreps, dx, dxa)
+            self._final_norm_bwd(form, saved, dreps, dx, dxa)
         for i in reversed(range(self.depth - 1 if pruned else self.depth)):
             s = saved["blocks"][i]
             rs_attn = None if dp is None else dp[2 * i]                        # this block's attention branch
@@ -941,23 +969,12 @@ class VisionTransformer(nn.Module):
         pend.flush()
         self._embed_bwd(saved, dx)
 
-    def _final_norm_bwd(self, saved, dreps, dx, dxa):
-        """Backward of the final norm on the CLS rows into the (zeroed) residual-stream gradient, and its bf16 copy.  A
-        segmented pass: on the gathered [nseg, 384] rows, then scattered to the CLS rows (sais_vit_cls_scatter_seg)."""
-        f, seg = self.flat, saved.get("seg")
-        if seg is not None:
-            dcls = torch.empty(seg.nseg, D, dtype=torch.float32, device=dx.device)
-            ops.layernorm_bwd(saved["x_final"], D, saved["meanN"], saved["rstdN"], f.w32("norm.weight"), seg.nseg, dy32=dreps,
-                              dx32=dcls, dgamma=f.g("norm.weight"), dbeta=f.g("norm.bias"))
-            ops.vit_cls_scatter_seg(dcls, seg, dx)
-        for g in saved["groups"] if seg is None else ():
-            r, fr = g["rows"], g["frames"]
-            ops.layernorm_bwd(saved["x_final"][r], g["ntok"] * D, saved["meanN"][fr], saved["rstdN"][fr], f.w32("norm.weight"),
-                              g["Fr"], dy32=dreps[fr], dx32=dx[r], lddx32=g["ntok"] * D, dgamma=f.g("norm.weight"),
-                              dbeta=f.g("norm.bias"))
+    def _final_norm_bwd(self, form, saved, dreps, dx, dxa):
+        """Backward of the final norm on the CLS rows into the (zeroed) residual-stream gradient, and its bf16 copy."""
+        f, dp = self.flat, saved["dp"]
+        form.cls_norm_bwd(saved, dreps, dx)
         # with DropPath the gradient that enters a branch is s dx (the residual stream keeps dx): the bf16 copies carry the
         # NEXT branch's scale — dxa feeds an MLP branch (2i + 1), dxb an attention branch (2i)
-        dp = saved.get("dp")
         if dp is None:
             ops.cast_bf16(dx, dxa)
         else:
@@ -989,14 +1006,7 @@ class VisionTransformer(nn.Module):
                               rowscale16=rs_attn)
         # attention branch
         ops.gemm_nt(dxb, f.wt16[p + "attn.proj.weight"], L.EPI_BIAS_BF16, dao)
-        if pl.seg is not None:                        # every frame of the pass in two launches
-            ops.vit_attn_bwd_seg(s["qkv"], dao, s["ao"], s["lse"][0], pl.seg, dqkv)
-        for g, lg in zip(pl.groups, s["lse"]) if pl.seg is None else ():
-            r = g["rows"]
-            if pl.streaming:
-                ops.vit_attn_bwd_any(s["qkv"][r], dao[r], s["ao"][r], lg, g["Fr"], g["ntok"], dqkv[r])
-            else:
-                ops.vit_attn_bwd(s["qkv"][r], dao[r], s["ao"][r], lg, None, g["Fr"], dqkv[r], ntok=g["ntok"])
+        pl.form.attn_bwd(s, dao, dqkv)
         # all four weight / bias gradients of the block in one launch.  (A side stream for this launch was measured
         # in round 1: 20.4 vs 19.6 ms/step — both kernels fill the chip — and removed.)
         dw = [(dxa, s["h"], f.g(p + "mlp.fc2.weight"), f.g(p + "mlp.fc2.bias")),
@@ -1018,21 +1028,10 @@ class VisionTransformer(nn.Module):
                               rowscale16=rs_prev)
 
     def _embed_bwd(self, saved, dx):
-        """Backward of the embedding per group (a segmented pass: sais_vit_embed_bwd_seg over all segments), then the patch
-        projection's weight gradient over all rows."""
-        f, seg = self.flat, saved.get("seg")
+        """Backward of the embedding in the pass's form, then the patch projection's weight gradient over all rows."""
+        f = self.flat
         dpatch = torch.empty(saved["patches"].shape[0], D, dtype=torch.bfloat16, device=dx.device)
-        if seg is not None:                         # one entry over all segments, through the per-axis taps: no [hw, 196] map
-            ops.vit_embed_bwd_seg(dx, seg, f.g("cls_token"), f.g("pos_embed"), dpatch)
-        for g in saved["groups"] if seg is None else ():
-            Fr, ntok = g["Fr"], g["ntok"]
-            dxg, dpg = dx[g["rows"]], dpatch[g["prows"]]
-            if g["interp"] is None:
-                ops.vit_embed_bwd(dxg, Fr, f.g("cls_token"), f.g("pos_embed"), dpg)
-            else:                                   # through the transpose of the bicubic map (autograd of :174-194)
-                dpos = torch.zeros(ntok, D, dtype=torch.float32, device=dx.device)
-                ops.vit_embed_bwd(dxg, Fr, f.g("cls_token"), dpos, dpg, ntok=ntok)
-                ops.pos_interp_bwd(g["interp"], dpos, f.g("pos_embed").view(NTOK, D))
+        saved["form"].embed_bwd(dx, dpatch)
         # (the ping-pong 128 x 384 dW kernel is no better here: 6 wide tiles x 42 row splits, 77 us against 65-68 us)
         ops.gemm_tn(dpatch, saved["patches"], f.g("patch_embed.proj.weight").view(D, PATCH_K),
                     f.g("patch_embed.proj.bias"))

@@ -15,7 +15,8 @@ are logged with their flops / bytes (`ops._timed` is wrapped), gradient hooks lo
 
 How device tensors are stood in for without a GPU: the cases run on CPU tensors.  `torch.Tensor.is_cuda` is overridden to
 answer True (the package refuses host tensors), `ops._stream()` gives NULL, `torch.cuda.is_current_stream_capturing()` and
-`torch.cuda.is_available()` are constants.  Nothing is computed, so outputs hold whatever `torch.empty` returned: no host
+`torch.cuda.is_available()` are constants; `vit_seg.SegPlan.to_device` logs the sha256 of the plan's host buffer (so the plan's
+contents are part of the record) and stands a CPU tensor over the same bytes in for the device copy.  Nothing is computed, so outputs hold whatever `torch.empty` returned: no host
 decision of the package depends on a kernel's result.  The pure host functions of the library (`sais_tgemm_nsplit`,
 `sais_workspace_bytes`, ...) are the real ones: the library must be built, it is only never asked to launch.
 Only names that bench.py, the tests and tools/ rely on are used, so the same file runs against older trees.
@@ -77,8 +78,9 @@ REC = Recorder()
 
 
 def install_recorder():
+    import hashlib
     import torch
-    from sais_amd import _lib, ops
+    from sais_amd import _lib, ops, vit_seg
     _lib.call = REC.call
     real_p, real_items = ops._p, ops.tn_items
 
@@ -97,6 +99,12 @@ def install_recorder():
             REC.log.append(["timer", tag, repr(float(flops)), int(nbytes)])
         fn()
 
+    def to_device(plan, device):                 # the plan's contents are part of the record; no pinned copy without a GPU
+        REC.log.append(["segplan", hashlib.sha256(plan.host.tobytes()).hexdigest()])
+        plan.dev = torch.from_numpy(plan.host)
+        return plan
+
+    vit_seg.SegPlan.to_device = to_device
     ops._p, ops.tn_items, ops._timed, ops._stream = _p, tn_items, _timed, lambda: None
     torch.Tensor.is_cuda = property(lambda self: True)
     torch.cuda.is_current_stream_capturing = lambda: False
@@ -422,6 +430,123 @@ def _add_vit_cases():
             m._forward_kernels([torch.zeros(2, 3, 224, 224).to(dev), torch.zeros(3, 3, 96, 96).to(dev)], save=False)
 
 
+def _add_vit_form_cases():
+    """The three forms of a ViT pass (resident, streaming, segmented) in both directions, patch 8, the retrieval tails and the
+    combinations the package refuses.  depth = 2 unless a case needs more."""
+    import torch
+    from sais_amd import ops
+    from sais_amd.vit import vit_small
+    MIXED = ((1, 224, 224), (2, 64, 96), (1, 160, 272))
+
+    def model(dev, train=False, dpr=0.0, depth=2, patch=16, **attrs):
+        m = vit_small(patch_size=patch, depth=depth, drop_path_rate=dpr).to(dev)
+        m.train(train)
+        m.grad_ready_hook = lambda lo, hi: REC.log.append(["hook", lo, hi])
+        for k, v in attrs.items():
+            setattr(m, k, v)
+        return m
+
+    def frames(dev, *shapes):
+        return [torch.zeros(n, 3, H, W).to(dev) for n, H, W in shapes]
+
+    def saved_pass(dev, shapes, seg=False, timer=False, **kw):
+        """_forward_kernels(save=True) + _backward_kernels on resolution groups, or on the frames as segments."""
+        m, x = model(dev, **kw), frames(dev, *shapes)
+        m._engine(dev)
+        old = ops.TIMER
+        if timer:
+            ops.TIMER = ops.KernelTimer()
+        try:
+            reps, saved = m._forward_kernels(x, save=True, streaming=True if seg else m.streaming_pass(x),
+                                             seg=m._seg_plan(x) if seg else None)
+            m._backward_kernels(saved, torch.ones_like(reps))
+        finally:
+            ops.TIMER = old
+
+    def train_step(dev, x, timer=False, **kw):
+        m, old = model(dev, **kw), ops.TIMER
+        if timer:
+            ops.TIMER = ops.KernelTimer()
+        try:
+            m(x).sum().backward()
+        finally:
+            ops.TIMER = old
+
+    for tag, kw in (("", {}), (" droppath", dict(train=True, dpr=0.1))):
+        case("vit streaming train 2 x 64x96" + tag)(lambda dev, kw=kw: train_step(dev, frames(dev, (2, 64, 96))[0], **kw))
+        case("vit streaming train 1 x 224x240" + tag)(lambda dev, kw=kw: train_step(dev, frames(dev, (1, 224, 240))[0], **kw))
+        case("vit streaming saved list pass" + tag)(lambda dev, kw=kw: saved_pass(dev, ((2, 224, 224), (3, 96, 128)), **kw))
+        for prune in (True, False):
+            for name, shapes in (("2x224 3x96", ((2, 224, 224), (3, 96, 96))), ("48x224 256x96", ((48, 224, 224), (256, 96, 96)))):
+                case("vit resident saved list pass %s prune=%d%s" % (name, prune, tag))(
+                    lambda dev, kw=kw, shapes=shapes, prune=prune: saved_pass(dev, shapes, prune_last_block=prune, **kw))
+        case("vit segmented train" + tag)(lambda dev, kw=kw: train_step(dev, frames(dev, *MIXED), **kw))
+        case("vit segmented train timer" + tag)(lambda dev, kw=kw: train_step(dev, frames(dev, *MIXED), timer=True, **kw))
+        case("vit segmented train 48 x 224x224" + tag)(lambda dev, kw=kw: train_step(dev, frames(dev, (48, 224, 224)), **kw))
+        case("vit segmented saved pass" + tag)(lambda dev, kw=kw: saved_pass(dev, MIXED, seg=True, **kw))
+
+    def frozen(dev, call, shapes=MIXED, depth=2, patch=16):
+        m = model(dev, depth=depth, patch=patch)
+        with torch.no_grad():
+            call(m, frames(dev, *shapes))
+
+    case("vit segmented dense_features n=2")(lambda dev: frozen(dev, lambda m, x: m.dense_features(x, 2)))
+    case("vit segmented retrieval_features cls_only")(lambda dev: frozen(dev, lambda m, x: m.retrieval_features(x, cls_only=True)))
+    case("vit segmented forward no_grad")(lambda dev: frozen(dev, lambda m, x: m(x)))
+    case("vit segmented forward no_grad 48 x 224x224")(lambda dev: frozen(dev, lambda m, x: m(x), ((48, 224, 224),)))
+    for cls_only in (False, True):
+        case("vit retrieval_features 2 x 160x272 cls_only=%d" % cls_only)(
+            lambda dev, c=cls_only: frozen(dev, lambda m, x: m.retrieval_features(x[0], cls_only=c), ((2, 160, 272),)))
+        case("vit8 retrieval_features 2 x 64x96 cls_only=%d" % cls_only)(
+            lambda dev, c=cls_only: frozen(dev, lambda m, x: m.retrieval_features(x[0], cls_only=c), ((2, 64, 96),), patch=8))
+    for name, call, shapes, depth in (
+            ("forward 2 x 224x224", lambda m, x: m(x[0]), ((2, 224, 224),), 2),
+            ("forward 2 x 64x96", lambda m, x: m(x[0]), ((2, 64, 96),), 2),
+            ("dense_features n=2", lambda m, x: m.dense_features(x[0], 2), ((2, 64, 96),), 2),
+            ("get_intermediate_layers n=2", lambda m, x: m.get_intermediate_layers(x[0], 2), ((2, 64, 96),), 2),
+            ("probe_features n=4", lambda m, x: m.probe_features(x[0], 4), ((2, 64, 96),), 4),
+            ("probe_features avgpool", lambda m, x: m.probe_features(x[0], 1, avgpool=True), ((2, 64, 96),), 2),
+            ("cls_attention", lambda m, x: m.cls_attention(x[0]), ((2, 64, 96),), 2)):
+        case("vit8 " + name)(lambda dev, a=(call, shapes, depth): frozen(dev, *a, patch=8))
+
+    def multicrop(dev, segmented):
+        from sais_amd.dino import MultiCropWrapper
+        old = os.environ.pop("SAIS_DINO_SEGMENTED", None)
+        if segmented:
+            os.environ["SAIS_DINO_SEGMENTED"] = "1"
+        try:
+            w = MultiCropWrapper(model(dev), _small_head())
+        finally:
+            os.environ.pop("SAIS_DINO_SEGMENTED", None)
+            if old is not None:
+                os.environ["SAIS_DINO_SEGMENTED"] = old
+        w.head._engine(dev)
+        logits, saved = w.forward_kernels(frames(dev, *([(2, 224, 224)] * 2 + [(2, 96, 96)] * 3)), save=True)
+        w.backward_kernels(saved, torch.zeros_like(logits))
+
+    case("MultiCropWrapper 2 global + 3 local crops")(lambda dev: multicrop(dev, False))
+    case("MultiCropWrapper 2 global + 3 local crops SAIS_DINO_SEGMENTED=1")(lambda dev: multicrop(dev, True))
+
+    def refused(dev, call, shapes=((1, 32, 48),), patch=16, grad=False):
+        m = model(dev, patch=patch)
+        m._engine(dev)
+        with torch.set_grad_enabled(grad):
+            call(m, frames(dev, *shapes))
+
+    for name, end in (("streaming=False", "reps"), ("end=probs", "probs"), ("end=norm1", "norm1")):
+        case("vit refuses seg with " + name)(lambda dev, end=end, s=name != "streaming=False": refused(
+            dev, lambda m, x: m._forward_kernels(x, save=False, end=end, streaming=s, seg=m._seg_plan(x))))
+    case("vit refuses seg of other rows")(lambda dev: refused(
+        dev, lambda m, x: m._forward_kernels(x, save=False, streaming=True, seg=m._seg_plan(x[:1])), ((1, 32, 48), (1, 64, 64))))
+    case("vit8 refuses a list: dense_features")(lambda dev: refused(dev, lambda m, x: m.dense_features(x), patch=8))
+    case("vit8 refuses a list: forward")(lambda dev: refused(dev, lambda m, x: m(x), patch=8))
+    case("vit8 refuses forward under grad")(lambda dev: refused(dev, lambda m, x: m(x[0]), patch=8, grad=True))
+    case("vit refuses an empty list")(lambda dev: refused(dev, lambda m, x: m([])))
+    case("vit refuses retrieval_features(list) without cls_only")(lambda dev: refused(dev, lambda m, x: m.retrieval_features(x)))
+    case("vit refuses probs of two groups")(lambda dev: refused(
+        dev, lambda m, x: m._forward_kernels(x, save=False, end="probs"), ((1, 224, 224), (1, 96, 96))))
+
+
 # ------------------------------------------------------------------------------------------------ driver
 def run(root, out, real):
     sys.path.insert(0, os.path.abspath(root))
@@ -432,6 +557,7 @@ def run(root, out, real):
     _add_inference_cases()
     _add_freshness_cases()
     _add_vit_cases()
+    _add_vit_form_cases()
     dev = torch.device("cuda:0" if real else "cpu")
     logs, results = {}, {}
     for i, (name, fn, in_real) in enumerate(CASES):
