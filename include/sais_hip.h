@@ -479,8 +479,19 @@ int sais_scale_f32(float* p, long n, float s, void* stream);
  * CenterCrop((height_frac*H, width_frac*W)) -> Resize((224,224)) -> ToTensor -> Normalize(mean, std), bit-identical to
  * torchvision 0.9.0 + Pillow's 8-bit bilinear resampler.  A plan holds the per-geometry coefficient tables on the
  * device (built once: allocation + upload); sais_preprocess_run only launches, so it can be graph-captured.
- * frames: device uint8 [F, H, W, 3] (RGB, as decoded); out: device float32 [F, 3, 224, 224].                      */
+ * frames: device uint8 [F, H, W, 3] (RGB, as decoded); out: device float32 [F, 3, 224, 224].  `frames` must be 4-byte
+ * aligned (the kernel reads it as dwords aligned from that pointer): sais_preprocess_run returns SAIS_ERR_ARG otherwise.
+ * A slice of a batch whose frames have H*W*3 % 4 != 0 need not be; copy it first.
+ * sais_preprocess_plan_describe is the geometry half of plan_create on the host alone (no device call, same refusals
+ * and codes): info = left, top, cw, ch (the crop box), kx, ky (Pillow's ksize per axis), band (output rows per
+ * workgroup: 8, 4, 2 or 1), nbands, max_rows (input rows of the tallest band), lds_bytes.  The horizontal pass runs
+ * (kx + 3) >> 2 groups of four taps up to kx = 32 and a byte-wise loop past it.  Additive: the ABI version stays.    */
+#define SAIS_PREPROCESS_INFO_INTS 10
+/* 1 where Pillow resamples a cw x ch crop box vertical pass first (more than 100 rows per column, height reduced): the
+ * plan then runs a second, plain kernel in that order (the passes round to uint8 in between, so the order shows).     */
+int  sais_preprocess_vertical_first(int cw, int ch);
 typedef struct SaisPreprocessPlan SaisPreprocessPlan;
+int  sais_preprocess_plan_describe(int H, int W, double height_frac, double width_frac, int* info /* [10] */);
 int  sais_preprocess_plan_create(int H, int W, double height_frac, double width_frac, const float* mean3,
                                  const float* std3, SaisPreprocessPlan** plan);
 int  sais_preprocess_plan_box(const SaisPreprocessPlan* plan, int* box4 /* left, top, right, bottom */);

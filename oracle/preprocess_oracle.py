@@ -81,8 +81,18 @@ def resample_axis0(img, out_size):
     return out
 
 
+def vertical_first(in_w, in_h, out_h=OUT_SIZE):
+    """Pillow 12.2, observed (tests/test_preprocess_edges_host.py): an image of more than 100 rows per column whose height is
+    being reduced is resampled vertical pass first.  The passes round to uint8 in between, so the order shows."""
+    return in_h > out_h and in_h > 100 * in_w
+
+
 def resize_bilinear_u8(img, out_h=OUT_SIZE, out_w=OUT_SIZE):
-    """Image.resize((out_w, out_h), BILINEAR) of a uint8 [H, W, C] array: horizontal pass first, then vertical."""
+    """Image.resize((out_w, out_h), BILINEAR) of a uint8 [H, W, C] array: horizontal pass first, then vertical, except for the
+    tall and narrow images of vertical_first."""
+    if vertical_first(img.shape[1], img.shape[0], out_h):
+        tmp = resample_axis0(np.ascontiguousarray(img), out_h)                                      # [out_h, W, C]
+        return resample_axis0(np.ascontiguousarray(tmp.transpose(1, 0, 2)), out_w).transpose(1, 0, 2)
     tmp = resample_axis0(np.ascontiguousarray(img.transpose(1, 0, 2)), out_w).transpose(1, 0, 2)    # [H, out_w, C]
     return resample_axis0(np.ascontiguousarray(tmp), out_h)
 

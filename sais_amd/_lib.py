@@ -206,6 +206,8 @@ SIGNATURES = {
     "sais_transpose_batch": [c_void_p, c_int, c_int, c_int, c_void_p],
     "sais_preprocess_plan_create": [c_int, c_int, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p,
                                     ctypes.POINTER(c_void_p)],
+    "sais_preprocess_plan_describe": [c_int, c_int, ctypes.c_double, ctypes.c_double, c_void_p],
+    "sais_preprocess_vertical_first": [c_int, c_int],
     "sais_preprocess_plan_box": [c_void_p, c_void_p],
     "sais_preprocess_run": [c_void_p, c_void_p, c_int, c_void_p, c_void_p],
     "sais_preprocess_plan_destroy": [c_void_p],

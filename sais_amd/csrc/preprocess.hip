@@ -12,6 +12,7 @@
 // make_axis / axis_coefs of resample.hpp that the kernels of augment.hip and imgfolder.hip run on the device.  The kernel
 // here is the tuned one of the three (host tables in global memory, dword loads): it does not use that header's band.
 #include <cmath>
+#include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -162,19 +163,71 @@ __global__ __launch_bounds__(256) void preprocess_kernel(Geometry g, const unsig
         }
     }
 }
+
+// Vertical pass first, for the tall and narrow boxes that Pillow resamples in that order (sais_preprocess_vertical_first):
+// the intermediate image is rounded to uint8 after the first pass, so the order shows in the result (by 1, in a fifth of
+// the bytes).  One workgroup per (frame, output row): the row's taps over every crop column go to LDS as uint8 [cw][3],
+// the horizontal pass reads them back.  Such boxes are at most VFIRST_MAX_CW columns wide and are not video frames: plain
+// byte loads, nothing tuned.
+constexpr int VFIRST_MAX_CW = 96;
+__global__ __launch_bounds__(256) void preprocess_vfirst_kernel(Geometry g, const unsigned char* frames, float* out) {
+    __shared__ unsigned char tmp[VFIRST_MAX_CW * 3];
+    const int yy = blockIdx.x, f = blockIdx.y, tid = threadIdx.x;
+    const int ymin = g.yb[2 * yy], cnt = g.yb[2 * yy + 1];
+    const int* k = g.yc + (size_t)yy * g.ky;
+    const size_t pitch = (size_t)g.W * 3;
+    for (int i = tid; i < g.cw * 3; i += 256) {
+        const unsigned char* p = frames + ((size_t)f * g.H + g.top + ymin) * pitch + (size_t)g.left * 3 + i;
+        int acc = 1 << (PRECISION_BITS - 1);
+        for (int y = 0; y < cnt; ++y) acc += p[y * pitch] * k[y];
+        tmp[i] = (unsigned char)clip8(acc);
+    }
+    __syncthreads();
+    for (int i = tid; i < 3 * OUT; i += 256) {
+        const int c = i / OUT, xx = i - c * OUT;
+        const int xmin = g.xb[2 * xx], n = g.xb[2 * xx + 1];
+        const int* kx = g.xc + (size_t)xx * g.kx;
+        int acc = 1 << (PRECISION_BITS - 1);
+        for (int x = 0; x < n; ++x) acc += tmp[(xmin + x) * 3 + c] * kx[x];
+        out[(((size_t)f * 3 + c) * OUT + yy) * OUT + xx] = g.lut[c * 256 + clip8(acc)];
+    }
+}
 }  // namespace
+
+// Pillow 12.2 resamples a box of more than 100 rows per column whose height is being reduced vertical pass first; every
+// other box horizontal pass first.  Observed, not read (its source is not part of this tree): at every width 3..96 the
+// switch is between ch = 100 cw and 100 cw + 1, at width 2 between ch = 224 and 225 (one column gives the same bytes
+// either way); a height that is enlarged goes horizontal first at any width (tests/test_preprocess_edges_host.py holds the rule against Pillow itself).
+extern "C" int sais_preprocess_vertical_first(int cw, int ch) { return cw > 0 && ch > OUT && (long)ch > 100L * cw; }
 
 struct SaisPreprocessPlan {
     Geometry g;
     int lds_bytes;
+    int vfirst;
     int* d_xb; int* d_xc; int* d_yb; int* d_yc; int* d_band; float* d_lut;
 };
 
-extern "C" int sais_preprocess_plan_create(int H, int W, double height_frac, double width_frac, const float* mean3,
-                                           const float* std3, SaisPreprocessPlan** plan) {
-    SAIS_ENTER();
-    if (!plan || !mean3 || !std3 || H <= 0 || W <= 0 || !(height_frac > 0 && height_frac <= 1) ||
-        !(width_frac > 0 && width_frac <= 1))
+// band b of `band` output rows: the crop rows its output rows read, as (first row, row count) pairs; returns the largest count
+static int band_extents(const resample::Axis& ay, int band, std::vector<int>* rows) {
+    int max_rows = 0;
+    for (int b0 = 0; b0 < OUT; b0 += band) {
+        int lo = 0, hi = 0;
+        for (int yy = b0; yy < OUT && yy < b0 + band; ++yy) {
+            int ymin, cnt;
+            double center;
+            resample::axis_bounds(ay, yy, ymin, cnt, center);
+            lo = yy == b0 ? ymin : std::min(lo, ymin);
+            hi = std::max(hi, ymin + cnt);
+        }
+        if (rows) { rows->push_back(lo); rows->push_back(hi - lo); }
+        max_rows = std::max(max_rows, hi - lo);
+    }
+    return max_rows;
+}
+
+// The geometry half of a plan, on the host alone: crop box, tap counts, band height and LDS size.
+extern "C" int sais_preprocess_plan_describe(int H, int W, double height_frac, double width_frac, int* info) {
+    if (!info || H <= 0 || W <= 0 || !(height_frac > 0 && height_frac <= 1) || !(width_frac > 0 && width_frac <= 1))
         return SAIS_ERR_ARG;
     // torchvision 0.9.0 center_crop with float sizes, then PIL's Image.crop rounding of every box edge
     // (Python round() = round-half-to-even = nearbyint in the default rounding mode)
@@ -183,28 +236,36 @@ extern "C" int sais_preprocess_plan_create(int H, int W, double height_frac, dou
     const int x0 = (int)std::nearbyint((double)left), y0 = (int)std::nearbyint((double)top);
     const int x1 = (int)std::nearbyint(left + cw), y1 = (int)std::nearbyint(top + ch);
     if (x0 < 0 || y0 < 0 || x1 > W || y1 > H || x1 <= x0 || y1 <= y0) return SAIS_ERR_ARG;
-    const AxisTable ax = make_table(x1 - x0), ay = make_table(y1 - y0);
+    const resample::Axis ax = resample::make_axis(x1 - x0, OUT, resample::BILINEAR);
+    const resample::Axis ay = resample::make_axis(y1 - y0, OUT, resample::BILINEAR);
 
     // band height: the largest of 8,4,2,1 output rows whose input rows fit the LDS budget
     int band = 8, max_rows = 0;
-    std::vector<int> band_rows;
     for (;; band >>= 1) {
-        band_rows.clear();
-        max_rows = 0;
-        for (int b0 = 0; b0 < OUT; b0 += band) {
-            int lo = ay.bounds[2 * b0], hi = 0;
-            for (int yy = b0; yy < OUT && yy < b0 + band; ++yy) {
-                lo = std::min(lo, ay.bounds[2 * yy]);
-                hi = std::max(hi, ay.bounds[2 * yy] + ay.bounds[2 * yy + 1]);
-            }
-            band_rows.push_back(lo);
-            band_rows.push_back(hi - lo);
-            max_rows = std::max(max_rows, hi - lo);
-        }
+        max_rows = band_extents(ay, band, nullptr);
         if (max_rows * ROW_BYTES + 16 + 3 * 256 * 4 <= LDS_BUDGET || band == 1) break;
     }
     const int fixed_bytes = ((max_rows * ROW_BYTES + 15) & ~15) + 3 * 256 * 4;
-    if (fixed_bytes > LDS_BUDGET) return SAIS_ERR_ARG;                   // > ~85x vertical downscale
+    // one output row alone reads up to 2 ch / 224 + 1 input rows of 672 B and 86 rows fit: refused above a 43x vertical
+    // downscale, i.e. from a crop height of 9634
+    if (fixed_bytes > LDS_BUDGET) return SAIS_ERR_ARG;
+    const int v[SAIS_PREPROCESS_INFO_INTS] = {x0, y0, x1 - x0, y1 - y0, ax.ksize, ay.ksize, band, (OUT + band - 1) / band,
+                                              max_rows, fixed_bytes};
+    std::memcpy(info, v, sizeof(v));
+    return SAIS_OK;
+}
+
+extern "C" int sais_preprocess_plan_create(int H, int W, double height_frac, double width_frac, const float* mean3,
+                                           const float* std3, SaisPreprocessPlan** plan) {
+    SAIS_ENTER();
+    if (!plan || !mean3 || !std3) return SAIS_ERR_ARG;
+    int info[SAIS_PREPROCESS_INFO_INTS];
+    const int rc = sais_preprocess_plan_describe(H, W, height_frac, width_frac, info);
+    if (rc != SAIS_OK) return rc;
+    const int x0 = info[0], y0 = info[1], cw = info[2], ch = info[3], band = info[6], nbands = info[7], max_rows = info[8];
+    const AxisTable ax = make_table(cw), ay = make_table(ch);
+    std::vector<int> band_rows;
+    band_extents(resample::make_axis(ch, OUT, resample::BILINEAR), band, &band_rows);
 
     std::vector<float> lut(3 * 256);
     for (int c = 0; c < 3; ++c)
@@ -221,10 +282,15 @@ extern "C" int sais_preprocess_plan_create(int H, int W, double height_frac, dou
         sais_preprocess_plan_destroy(p);
         return SAIS_ERR_LAUNCH;
     }
-    p->g = Geometry{H, W, x0, y0, x1 - x0, y1 - y0, ax.ksize, ay.ksize, band, (OUT + band - 1) / band, max_rows,
+    p->g = Geometry{H, W, x0, y0, cw, ch, info[4], info[5], band, nbands, max_rows,
                     0L,
                     p->d_xb, p->d_xc, p->d_yb, p->d_yc, p->d_band, p->d_lut};
-    p->lds_bytes = fixed_bytes;
+    p->lds_bytes = info[9];
+    p->vfirst = sais_preprocess_vertical_first(cw, ch);
+    if (p->vfirst && cw > VFIRST_MAX_CW) {          // cannot happen below the refused crop heights (ch <= 9633 < 100 * 97)
+        sais_preprocess_plan_destroy(p);
+        return SAIS_ERR_ARG;
+    }
     *plan = p;
     return SAIS_OK;
 }
@@ -240,10 +306,14 @@ extern "C" int sais_preprocess_run(const SaisPreprocessPlan* plan, const unsigne
                                    void* stream) {
     SAIS_ENTER();
     if (!plan || !frames || !out || nframes <= 0) return SAIS_ERR_ARG;
+    if ((uintptr_t)frames & 3) return SAIS_ERR_ARG;          // the kernel reads frames as dwords aligned from this pointer
     Geometry g = plan->g;
     g.total_bytes = (long)nframes * g.H * g.W * 3;
-    hipLaunchKernelGGL(preprocess_kernel, dim3(g.nbands, nframes), dim3(256), plan->lds_bytes, (hipStream_t)stream,
-                       g, frames, out);
+    if (plan->vfirst)
+        hipLaunchKernelGGL(preprocess_vfirst_kernel, dim3(OUT, nframes), dim3(256), 0, (hipStream_t)stream, g, frames, out);
+    else
+        hipLaunchKernelGGL(preprocess_kernel, dim3(g.nbands, nframes), dim3(256), plan->lds_bytes, (hipStream_t)stream,
+                           g, frames, out);
     return sais_check_launch();
 }
 

@@ -79,7 +79,11 @@ __global__ __launch_bounds__(256) void lookup_kernel(LookupParams p) {
     // the window offsets are integers: every sample of the window has the same fractional part
     const float fx0 = floorf(cx), fy0 = floorf(cy);
     const float fx = cx - fx0, fy = cy - fy0;
-    const int x0 = (int)fx0 - r, y0 = (int)fy0 - r;
+    // clamped to +-2^30 before the conversion: a coordinate past the int range saturates to INT_MAX, x0 + a + 1 then
+    // overflows, and the compiler (free to assume it does not) tests x + 1 >= 0 as x > -2, so the wrapped index passed the
+    // bounds test and the tap was read 8 GB off its row.  A level is under 2^28 wide: clamped windows stay outside it.
+    constexpr float WIN_LIM = 1073741824.0f;
+    const int x0 = (int)fminf(fmaxf(fx0, -WIN_LIM), WIN_LIM) - r, y0 = (int)fminf(fmaxf(fy0, -WIN_LIM), WIN_LIM) - r;
     auto tap = [&](int x, int y) { return (x >= 0 && x < Wl && y >= 0 && y < Hl) ? img[y * Wl + x] : 0.f; };
     float* o = p.out + ((size_t)b * 4 * n * n + (size_t)l * n * n) * HW + pos;
     for (int a = 0; a < n; ++a) {                                    // a: along x (the published meshgrid order)

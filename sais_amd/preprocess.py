@@ -46,6 +46,8 @@ class FramePreprocessor:
         if frames.dtype != torch.uint8 or frames.dim() != 4 or tuple(frames.shape[1:]) != (self.height, self.width, 3):
             raise ValueError(f"expected uint8 [F,{self.height},{self.width},3], got {frames.dtype} {tuple(frames.shape)}")
         frames = frames.to(self.device, non_blocking=True).contiguous()
+        if frames.data_ptr() & 3:                    # a view that starts inside a dword: the kernel loads aligned dwords
+            frames = frames.clone()
         n = frames.shape[0]
         if out is None:
             out = torch.empty(n, 3, 224, 224, dtype=torch.float32, device=self.device)

@@ -48,6 +48,7 @@ def test_bad_arguments_are_rejected_without_a_gpu():
     assert lib.sais_dropout_f32(None, None, None, 10, 0.1, None, 0, None) == -1 and lib.sais_rng_advance(None, None) == -1
     assert lib.sais_preprocess_plan_create(0, 10, 0.8, 0.8, None, None, None) == -1
     assert lib.sais_preprocess_run(None, None, 1, None, None) == -1
+    assert lib.sais_preprocess_plan_describe(8, 8, 0.8, 0.8, None) == -1
     # DINO objective entries
     assert lib.sais_vit_attn_fwd(ctypes.c_void_p(16), 1152, 1, 50, ctypes.c_void_p(16), 384, None, None, None) == -1   # ntok
     assert lib.sais_patchify(ctypes.c_void_p(16), 1, 100, ctypes.c_void_p(16), None) == -1                            # side % 16

@@ -6,9 +6,9 @@ formula and uint8/255 -> (x-mean)/std, restated in oracle/preprocess_oracle.py."
 import numpy as np
 import pytest
 import torch
-from PIL import Image
 
 from oracle import preprocess_oracle as po
+from preprocess_ref import pil_pipeline as _pil_pipeline          # the one copy of the Pillow pipeline
 
 SIZES = [(1080, 1920), (480, 854), (231, 517), (224, 224), (300, 200), (97, 1033), (720, 1280), (61, 45)]
 
@@ -20,17 +20,6 @@ def _frame(h, w, seed, smooth=False):
         base = np.stack([127 + 120 * np.sin(xx / 37.0 + c) * np.cos(yy / 23.0 - c) for c in range(3)], -1)
         return np.clip(base + g.normal(0, 6, (h, w, 3)), 0, 255).astype(np.uint8)
     return g.integers(0, 256, (h, w, 3), dtype=np.uint8)
-
-
-def _pil_pipeline(frame, hf=0.8, wf=0.8):
-    """The reference's per-frame CPU pipeline with Pillow doing the work (torchvision 0.9.0 call sequence)."""
-    img = Image.fromarray(frame)
-    w, h = img.size
-    ch, cw = hf * h, wf * w
-    top, left = int(round((h - ch) / 2.)), int(round((w - cw) / 2.))
-    img = img.crop((left, top, left + cw, top + ch)).resize((224, 224), Image.BILINEAR)
-    t = torch.from_numpy(np.asarray(img).copy()).permute(2, 0, 1).float().div(255)
-    return t.sub_(torch.tensor(po.MEAN)[:, None, None]).div_(torch.tensor(po.STD)[:, None, None]).numpy()
 
 
 @pytest.mark.parametrize("hw", SIZES)
