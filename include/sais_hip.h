@@ -738,7 +738,10 @@ int sais_temporal_attn_bwd_long(const float* qkv, const unsigned char* key_pad, 
  * sais_rng_advance is a graph node), the site id and the element index; forward and backward regenerate them, nothing is
  * stored.  sais_dropout_f32: out = (resid ? resid : 0) + x * keep / (1 - p) (out may alias x); applied to a gradient with
  * the same (state, site) it is the backward of itself.  sais_dropout_mask exports the keep mask (tests feed it to the oracle).
- * The stream of numbers is this library's, not torch's: a torch run with the same seed draws different masks.            */
+ * The stream of numbers is this library's, not torch's: a torch run with the same seed draws different masks.
+ * The rule, for every site: the draw of element idx is word idx % 4 of Philox4x32-10 at counter {idx / 4 low word, idx / 4
+ * high word, site, offset low word} and key {seed low word, seed high word ^ offset high word}; the element is kept  <=>
+ * draw >= (unsigned)min(p * 2^32, 4294967040) with the product in fp32; kept values are scaled by the fp32 1 / (1 - p).   */
 int sais_rng_advance(unsigned long long* state /*{seed, offset}*/, void* stream);
 int sais_dropout_f32(const float* x, const float* resid /*optional*/, float* out, long n, float p,
                      const unsigned long long* rng_state, unsigned site, void* stream);

@@ -2,8 +2,10 @@
 // dropout as well, but the (seed, offset) -> element mapping here is this library's own, so masks are NOT torch's).
 // state = {seed, offset} lives in device memory (two uint64) so that a captured hipGraph draws fresh masks at every
 // replay: sais_rng_advance bumps `offset` inside the graph.  The mask of element `idx` of dropout site `sid`:
-//   r = philox(counter = {idx / 4 (64 bit), sid, offset}, key = seed)[idx % 4],   keep  <=>  r >= p * 2^32.
-// Forward and backward regenerate the same mask from (state, sid, idx): nothing is stored.
+//   r = philox(counter = {idx / 4 lo, idx / 4 hi, sid, offset lo}, key = {seed lo, seed hi ^ offset hi})[idx % 4],
+//   keep  <=>  r >= (unsigned)min(p * 2^32, 4294967040), the product in fp32.
+// Forward and backward regenerate the same mask from (state, sid, idx): nothing is stored.  tests/philox_ref.py is an
+// independent model of this rule; tests/test_dropout_edges_gpu.py holds every site that draws against it bit for bit.
 #pragma once
 #include "common.hpp"
 
